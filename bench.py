@@ -13,7 +13,13 @@ weights identical on every rank, FlatAdam(1e-4, (0.5, 0.9)).  The timed region i
 loss .item() syncs and the G-step's D2H copy of `fake` (they are part of the reference's trainer
 contract, train.py:39-42,74).  value = world * B * 8192 * K / max-over-ranks(wall time).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+A plain run measures the headline alone: set-up, the untimed priming and warm-up calls, the K timed steps, the
+JSON line.  --dump-outputs DIR then writes what the last timed step returned (the trainer's result dict: the loss,
+and for a G-step the generated batch `fake`) as DIR/<name>.npy, float32 arrays / float64 scalars; inputs and weights
+are seeded, so two builds given the same arguments can be compared output for output.
+
+Rank 0 prints ONE JSON line.  Extra objects, measured only with --full (each leg can still be left out with its
+--no-* switch; the layer-spec step_roofline of --model twostage / realmelgan is host arithmetic and is always there):
   roofline      dominant kernel (by device time in an instrumented eager D+G pass): algorithmic
                 FLOPs per launch / mean DEVICE duration of the launch (the dispatches' own begin / end
                 timestamps through hipExtLaunchKernelGGL events: what rocprofv3 reports; the stream-event
@@ -31,6 +37,8 @@ Rank 0 prints ONE JSON line.  Extra objects:
                 multiply as six exact bf16 partial products (no 22-bit operand anywhere)
   cpu_baseline  the torch-functional CPU restatement of the reference graph (oracle/torch_graph.py)
                 timed on this host's cores on a bounded sample (N=1 runs only)
+  dp_overhead   the N = 1 step under the data-parallel control flow against the plain step (child processes, N=1 only)
+  generator_forward_b1  BASELINE config 2: hipGraph replay latency of the generator forward at B=1
 """
 import argparse
 import json
@@ -129,6 +137,31 @@ def launch_workers(args):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs: at most this many bytes of array data in all
+
+
+def dump_outputs(out_dir, res):
+    """A trainer call's result dict -> out_dir/<name>.npy: numbers as float64 scalars, arrays as float32.  Should the
+    arrays exceed DUMP_BYTES, each keeps a fixed, seeded sample of its elements (sorted flat indices)."""
+    import numpy as np
+    arrays = {}
+    for k, v in res.items():
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        if a.dtype.kind not in "biuf":
+            continue
+        arrays[k] = a.astype(np.float64) if a.ndim == 0 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in sorted(arrays.items()):
+        if total > DUMP_BYTES and a.ndim:
+            n = max(1, a.size * DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log("[bench] outputs of the last timed step -> %s: %s" % (out_dir, ", ".join(sorted(arrays))))
+
+
 def child_bench(args, env_extra, what):
     """The same bench (timed region only: no roofline / CPU / config-2 legs) in a fresh child process with extra environment
     switches -- the library reads its operand-scheme switches once per process.  The parent is idle meanwhile.
@@ -181,7 +214,17 @@ def main():
     ap.add_argument("--no-gforward", action="store_true",
                     help="skip the BASELINE config-2 leg (generator forward, B=1): keeps its B=1 dispatches out "
                          "of a rocprofv3 trace of the train step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs after the timed steps: roofline + step_roofline (instrumented eager pass), "
+                         "the config-2 generator forward, value_exact, dp_overhead and the CPU baseline (each still "
+                         "subject to its --no-* switch); without it a run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 arrays, float64 scalars)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_cpu_baseline = args.no_exact = args.no_dp_overhead = args.no_gforward = True
 
     # decided before torch is imported: a multi-GPU run not started by torchrun launches its own workers
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -290,9 +333,12 @@ def main():
     torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
-        last.update(call(i))
+        out = call(i)
+        last.update(out)
     torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)

@@ -52,7 +52,7 @@ if __name__ == "__main__":
     else:
         for name in PATCHES:
             env = dict(os.environ, MSYNTH_LIB=os.path.join(OUT, "libmsynth_w_%s.so" % name))
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "6", "--no-cpu-baseline", "--no-exact",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "6", "--no-cpu-baseline", "--no-exact",
                                 "--no-dp-overhead", "--no-gforward"], env=env, capture_output=True, text=True)
             try:
                 d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -11,7 +11,7 @@ cd $R
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tests -- python3 -m pytest tests -m gpu -q -p no:cacheprovider --timeout=600 > $O/tests.log 2>&1; echo "tests rc=$? $(tail -1 $O/tests.log)"
 for m in headline twostage realmelgan; do
   extra=""; [ $m != headline ] && extra="--model $m"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$m -- python3 bench.py $extra --prime 0 --steps 4 --warmup 2 --no-cpu-baseline --no-exact --no-dp-overhead > $O/$m.json 2> $O/$m.log; echo "$m rc=$?"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$m -- python3 bench.py $extra --full --prime 0 --steps 4 --warmup 2 --no-cpu-baseline --no-exact --no-dp-overhead > $O/$m.json 2> $O/$m.log; echo "$m rc=$?"
 done
 python3 - <<'PY'
 import csv, glob, re
