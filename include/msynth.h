@@ -271,11 +271,13 @@ int ms_conv1d_img_fwd(const ms_conv1d_desc* d, const float* x, const void* image
 int ms_conv1d_img_bwd_data(const ms_conv1d_desc* d, const float* gy, const float* y_act, const void* image_bwd,
                            const float* gx_add, float* gx, void* workspace, size_t workspace_bytes, ms_stream_t stream);
 
-/* which: 0 fwd, 1 bwd_data, 2 bwd_weight */
+/* which: 0 fwd, 1 bwd_data, 2 bwd_weight.  Enough for every kernel the call may reach, with or without residual / y_act. */
 size_t ms_conv1d_workspace_bytes(const ms_conv1d_desc* d, int which);
 
 /* Name of the device kernel the dispatch selects for this geometry (which: 0 fwd, 1 bwd_data,
- * 2 bwd_weight) -- lets a profiler line be matched to a layer.  Static string, never NULL. */
+ * 2 bwd_weight) -- lets a profiler line be matched to a layer.  It describes a call without residual and
+ * without y_act (a forward with either may run another kernel); "" when the dispatch has no kernel for the
+ * geometry.  Static string, never NULL. */
 const char* ms_conv1d_kernel_name(const ms_conv1d_desc* d, int which);
 
 /* Profiling aid (off by default; never needed for normal operation).  ms_profile_kernels(1) opens a profile session of the

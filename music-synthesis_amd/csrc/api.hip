@@ -218,146 +218,152 @@ int ms_conv1d_out_len(const ms_conv1d_desc* d) {
     return make_conv(d, &p) ? p.Lout : MS_ERR_INVALID_ARG;
 }
 
+int ms_convt1d_out_len(const ms_convt1d_desc* d) {
+    ConvP p;
+    return make_convt(d, &p) ? p.Lin : MS_ERR_INVALID_ARG;
+}
+
+}  // extern "C"
+
+// ---- dispatch plans: which kernel a conv call runs
+// Decided here and nowhere else.  A plan lists the routes of one call in the order they are tried, up to the first route that
+// cannot pass the call on.  The entry points run the first route that takes the call; the queries read the same list: the
+// kernel name is the first route's, the workspace covers every route in the list, a parts call is one launch unless its
+// first route goes part by part.
+namespace {
+
+enum Kind {
+    F_THIN_SHORT, F_SMALL, F_PAD4, F_MFMA, F_G4, F_G3, F_G, F_THIN, F_DIRECT,    // ms_conv1d_fwd
+    D_PAD4, D_MFMA, D_G4, D_G3, D_G, D_THIN, D_DIRECT,                          // ms_conv1d_bwd_data (zero-padded geometry)
+    W_THIN, W_SHORT, W_32, W_K5, W_ROWS, W_MFMA, W_G4, W_G3, W_G, W_DIRECT,     // ms_conv1d_bwd_weight
+    TF_THIN, TF_LANES, TF_MFMA, TF_DIRECT,                                      // ms_convt1d_fwd (geometry: the mirrored conv)
+    TD_MFMA, TD_CONV_MFMA, TD_CONV_DIRECT,                                      // ms_convt1d_bwd_data
+    TW_THIN, TW_8, TW_2S, TW_MFMA, TW_CONV_MFMA, TW_CONV_DIRECT,                // ms_convt1d_bwd_weight
+    P_DISC, P_G4, P_K5, P_K5_IMG, P_G3, P_EACH,                                 // ms_conv1d_parts_* (P_EACH: part by part)
+};
+
+// Route::declines, how a route may pass the call on (0: it takes every call that reaches it): its launcher may return
+// MS_ERR_UNSUPPORTED (operand alignment and the like) / it is skipped when the workspace is short / not 16-byte aligned
+enum : unsigned { UNSUPPORTED = 1, SHORT_WS = 2, ALIGNED_WS = 4 };
+
+struct Route {
+    Kind kind;
+    unsigned declines;
+    ConvP g;           // the geometry it runs on
+    size_t ws;         // the workspace it needs
+};
+
+struct Plan {
+    int n = 0;
+    Route r[6];
+    Plan& add(Kind k, const ConvP& g, size_t ws = 0, unsigned declines = 0) {
+        r[n++] = Route{k, declines, g, ws};
+        return *this;
+    }
+    size_t ws() const {
+        size_t m = 0;
+        for (int i = 0; i < n; ++i) m = r[i].ws > m ? r[i].ws : m;
+        return m;
+    }
+};
+
 // a single tensor as a table of one part (the 4 x 4 group kernels of gconv4.hip take 1 .. 3 parts)
-static ms_conv1d_parts one_part(const ConvP& p) {
+ms_conv1d_parts one_part(const ConvP& p, const float* x = nullptr, float* y = nullptr, const float* gy = nullptr,
+                         const float* y_act = nullptr, const float* gx_add = nullptr, float* gx = nullptr) {
     ms_conv1d_parts q{};
     q.count = 1;
     q.B[0] = p.B; q.Lin[0] = p.Lin;
+    q.x[0] = x; q.y[0] = y; q.gy[0] = gy; q.y_act[0] = y_act; q.gx_add[0] = gx_add; q.gx[0] = gx;
     return q;
 }
 
-int ms_conv1d_fwd(const ms_conv1d_desc* d, const float* x, const float* w, const float* bias,
-                  const float* residual, float* y, float* y_act, void* workspace,
-                  size_t workspace_bytes, ms_stream_t stream) {
-    ConvP p;
-    if (!make_conv(d, &p) || !x || !w || !y) return MS_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    // activation in front of the conv: applied to x on load (operand modifier "LeakyReLU of the value")
-    const float* xa = p.in_act ? x : nullptr;
-    const int xk = p.in_act ? MS_MOD_LRELU_FWD : 0;
-    if (mst_fwd_short_applicable(p) && !y_act && !residual)   // judge conv: a 12-MFLOP reduction, not a GEMM
-        return mst_conv1d_fwd(p, x, w, bias, residual, y, s);
-    if (!y_act && !residual && mss_conv_applicable(p))        // a few dozen columns in the whole batch: a weight stream
-        return mss_conv_fwd(p, x, w, bias, y, s);
-    if (msm_fwd_applicable(p) && pad4_applicable(p) && !residual && !y_act) {
-        const ConvP q = pad4_conv(p);
-        const size_t xb = pad4_bytes(q, p.Cin), yb = pad4_bytes(q, p.Cout);
-        if (workspace && workspace_bytes >= xb + yb + msm_fwd_ws(q) && (((uintptr_t)workspace) & 15) == 0) {
-            float* xp = (float*)workspace;
-            float* yp = (float*)((char*)workspace + xb);
-            int rc = pad_rows(x, xp, (size_t)p.B * p.Cin, p.Lin, q.Lin, s);
-            if (rc != MS_OK) return rc;
-            rc = msm_conv1d_fwd(q, xp, nullptr, 0, w, bias, nullptr, yp, nullptr, (char*)workspace + xb + yb,
-                                workspace_bytes - xb - yb, s);
-            if (rc != MS_OK) return rc;
-            return unpad_rows(yp, nullptr, y, (size_t)p.B * p.Cout, p.Lin, q.Lin, s);
+// residual, y_act: the call has them.  A route that cannot decline ends the plan (return).
+Plan conv_plan(ConvP p, int which, bool residual, bool y_act) {
+    Plan pl;
+    const bool plain = !residual && !y_act;
+    if (which == 0) {
+        if (plain && mst_fwd_short_applicable(p)) return pl.add(F_THIN_SHORT, p);   // judge conv: a 12-MFLOP reduction, not a GEMM
+        if (plain && mss_conv_applicable(p)) return pl.add(F_SMALL, p);            // a few dozen columns in the whole batch
+        if (msm_fwd_applicable(p)) {
+            if (plain && pad4_applicable(p)) {
+                const ConvP q = pad4_conv(p);
+                pl.add(F_PAD4, q, pad4_bytes(q, p.Cin) + pad4_bytes(q, p.Cout) + msm_fwd_ws(q), SHORT_WS | ALIGNED_WS);
+            }
+            return pl.add(F_MFMA, p, msm_fwd_ws(p));
         }
-    }
-    if (msm_fwd_applicable(p))
-        return msm_conv1d_fwd(p, x, xa, xk, w, bias, residual, y, y_act, workspace, workspace_bytes, s);
-    if (!residual && !y_act && !p.in_act) {
-        ms_conv1d_parts q = one_part(p);
-        q.x[0] = x; q.y[0] = y;
-        if (msg4_parts_applicable(p, &q)) return msg4_parts_fwd(p, &q, w, bias, s);
-    }
-    if (msg3_fwd_applicable(p) && !residual && !y_act && !p.in_act) return msg3_conv1d_fwd(p, x, w, bias, y, s);
-    if (msg_fwd_applicable(p) && !residual && !y_act && !p.in_act) return msg_conv1d_fwd(p, x, w, bias, y, s);
-    if (mst_fwd_applicable(p) && !y_act) return mst_conv1d_fwd(p, x, w, bias, residual, y, s);
-    return msk_conv1d_fwd_direct(p, x, xa, xk, w, bias, residual, y, y_act, s);
-}
-
-int ms_conv1d_bwd_data(const ms_conv1d_desc* d, const float* gy, const float* y_act,
-                       const float* w, const float* gx_add, float* gx, void* workspace,
-                       size_t workspace_bytes, ms_stream_t stream) {
-    ConvP p;
-    if (!make_conv(d, &p) || !gy || !w || !gx) return MS_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    // reflection padding: the zero-padded backward gives the gradient of the in-range taps; the
-    // taps that read mirrored samples are folded back onto their sources by a small edge kernel
-    const bool reflect = p.pad_mode == MS_PAD_REFLECT;
-    if (reflect && (p.stride != 1 || p.groups != 1)) return MS_ERR_UNSUPPORTED;
-    p.pad_mode = MS_PAD_ZERO;
-    int rc;
-    bool padded = false;
-    if (msm_bwd_data_applicable(p) && pad4_applicable(p)) {
-        const ConvP q = pad4_conv(p);
-        const size_t gb = pad4_bytes(q, p.Cout), xb = pad4_bytes(q, p.Cin);
-        const size_t need = gb * (y_act ? 2 : 1) + xb + msm_bwd_data_ws(q);
-        if (workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 15) == 0) {
-            char* wsp = (char*)workspace;
-            float* gp = (float*)wsp; wsp += gb;
-            float* ap = nullptr;
-            if (y_act) { ap = (float*)wsp; wsp += gb; }
-            float* xp = (float*)wsp; wsp += xb;
-            rc = pad_rows(gy, gp, (size_t)p.B * p.Cout, p.Lin, q.Lin, s);
-            if (rc == MS_OK && y_act) rc = pad_rows(y_act, ap, (size_t)p.B * p.Cout, p.Lin, q.Lin, s);
-            if (rc == MS_OK)
-                rc = msm_conv1d_bwd_data(q, gp, ap, w, nullptr, xp, wsp, workspace_bytes - (size_t)(wsp - (char*)workspace), s);
-            if (rc == MS_OK) rc = unpad_rows(xp, gx_add, gx, (size_t)p.B * p.Cin, p.Lin, q.Lin, s);
-            padded = true;
+        if (plain && !p.in_act) {
+            const ms_conv1d_parts q = one_part(p);
+            if (msg4_parts_applicable(p, &q)) return pl.add(F_G4, p);
+            if (msg3_fwd_applicable(p)) return pl.add(F_G3, p);
+            if (msg_fwd_applicable(p)) return pl.add(F_G, p);
         }
+        if (mst_fwd_applicable(p) && !y_act) return pl.add(F_THIN, p);
+        return pl.add(F_DIRECT, p);
     }
-    if (padded) {
-    } else if (msm_bwd_data_applicable(p))
-        rc = msm_conv1d_bwd_data(p, gy, y_act, w, gx_add, gx, workspace, workspace_bytes, s);
-    else if (ms_conv1d_parts q4 = one_part(p); msg4_parts_applicable(p, &q4)) {
-        q4.gy[0] = gy; q4.y_act[0] = y_act; q4.gx_add[0] = gx_add; q4.gx[0] = gx;
-        rc = msg4_parts_bwd_data(p, &q4, w, s);
-    } else if (msg3_bwd_data_applicable(p))
-        rc = msg3_conv1d_bwd_data(p, gy, y_act, w, gx_add, gx, s);
-    else if (msg_bwd_data_applicable(p))
-        rc = msg_conv1d_bwd_data(p, gy, y_act, w, gx_add, gx, s);
-    else if (mst_bwd_data_applicable(p) && !reflect)
-        rc = mst_conv1d_bwd_data(p, gy, y_act, w, gx_add, gx, s);
-    else
-        rc = msk_conv1d_bwd_data_direct(p, gy, y_act, w, nullptr, MS_ACT_NONE, gx_add, gx, s);
-    if (rc != MS_OK || !reflect) return rc;
-    return msk_reflect_fold_bwd(p, gy, y_act, w, gx, s);
-}
-
-int ms_conv1d_bwd_weight(const ms_conv1d_desc* d, const float* x, const float* gy,
-                         const float* y_act, float* gw, float* gb, float beta, void* workspace,
-                         size_t workspace_bytes, ms_stream_t stream) {
-    ConvP p;
-    if (!make_conv(d, &p) || !x || !gy || !gw) return MS_ERR_INVALID_ARG;
-    if (beta != 0.f && beta != 1.f) return MS_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const float* xa = p.in_act ? x : nullptr;
-    const int xk = p.in_act ? MS_MOD_LRELU_FWD : 0;
-    if (mst_bwd_weight_applicable(p))   // one-channel side: HBM-bound stream kernels
-        return mst_conv1d_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-    if (msws_applicable(p) && workspace && workspace_bytes >= msws_ws(p)) {     // reflection-padded conv on short rows
-        const int rc = msws_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-        if (rc != MS_ERR_UNSUPPORTED) return rc;
+    if (which == 1) {
+        // reflection padding: the zero-padded backward gives the gradient of the in-range taps; the taps that read mirrored
+        // samples are folded back onto their sources by an edge kernel behind (ms_conv1d_bwd_data)
+        const bool reflect = p.pad_mode == MS_PAD_REFLECT;
+        if (reflect && (p.stride != 1 || p.groups != 1)) return pl;
+        p.pad_mode = MS_PAD_ZERO;
+        if (msm_bwd_data_applicable(p)) {
+            if (pad4_applicable(p)) {        // padded copies of gy (and y_act) and gx + the padded problem's own workspace
+                const ConvP q = pad4_conv(p);
+                pl.add(D_PAD4, q, pad4_bytes(q, p.Cout) * (y_act ? 2 : 1) + pad4_bytes(q, p.Cin) + msm_bwd_data_ws(q),
+                       SHORT_WS | ALIGNED_WS);
+            }
+            return pl.add(D_MFMA, p, msm_bwd_data_ws(p));
+        }
+        const ms_conv1d_parts q = one_part(p);
+        if (msg4_parts_applicable(p, &q)) return pl.add(D_G4, p);
+        if (msg3_bwd_data_applicable(p)) return pl.add(D_G3, p);
+        if (msg_bwd_data_applicable(p)) return pl.add(D_G, p);
+        if (mst_bwd_data_applicable(p) && !reflect) return pl.add(D_THIN, p);
+        return pl.add(D_DIRECT, p);
     }
-    if (msw32_applicable(p)) {          // 32 -> 32 k3 atoms: HBM-bound, per-wave units
-        const int rc = msw32_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-        if (rc != MS_ERR_UNSUPPORTED) return rc;
-    }
-    if (msw5_applicable(p) && workspace && workspace_bytes >= msw5_ws(p))    // 1024 -> 1024 k5 on short rows
-        return msw5_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-    if (msw_bwd_weight_applicable(p)) { // dense stride-1 convs: row-tile MFMA form
-        const int rc = msw_conv1d_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-        if (rc != MS_ERR_UNSUPPORTED) return rc;     // (unaligned operands: the im2col form below)
-    }
-    if (msm_bwd_weight_applicable(p))
-        return msm_conv1d_bwd_weight(p, x, xa, xk, gy, y_act, p.act, gw, gb, beta, workspace,
-                                     workspace_bytes, s);
+    if (mst_bwd_weight_applicable(p)) return pl.add(W_THIN, p, mst_bwd_weight_ws(p));   // one-channel side: HBM-bound streams
+    if (msws_applicable(p)) pl.add(W_SHORT, p, msws_ws(p), SHORT_WS | UNSUPPORTED);    // reflection-padded conv on short rows
+    if (msw32_applicable(p)) pl.add(W_32, p, msw32_ws(p), UNSUPPORTED);               // 32 -> 32 k3 atoms: per-wave units
+    if (msw5_applicable(p)) pl.add(W_K5, p, msw5_ws(p), SHORT_WS);                    // 1024 -> 1024 k5 on short rows
+    if (msw_bwd_weight_applicable(p)) pl.add(W_ROWS, p, msw_bwd_weight_ws(p), UNSUPPORTED);   // dense stride-1: row tiles
+    if (msm_bwd_weight_applicable(p)) return pl.add(W_MFMA, p, msm_bwd_weight_ws(p));
     if (!p.in_act) {
-        ms_conv1d_parts q = one_part(p);
-        q.x[0] = x; q.gy[0] = gy; q.y_act[0] = y_act;
-        if (msg4_parts_applicable(p, &q)) return msg4_parts_bwd_weight(p, &q, gw, gb, beta, s);
+        const ms_conv1d_parts q = one_part(p);
+        if (msg4_parts_applicable(p, &q)) return pl.add(W_G4, p);
+        if (msg3_bwd_weight_applicable(p)) return pl.add(W_G3, p, msg_bwd_weight_ws(p));
+        if (msg_bwd_weight_applicable(p)) return pl.add(W_G, p, msg_bwd_weight_ws(p));
     }
-    if (msg3_bwd_weight_applicable(p) && !p.in_act)
-        return msg3_conv1d_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-    if (msg_bwd_weight_applicable(p) && !p.in_act)
-        return msg_conv1d_bwd_weight(p, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
-    return msk_conv1d_bwd_weight_direct(p, x, xa, xk, gy, y_act, p.act, gw, gb, beta, workspace,
-                                        workspace_bytes, s);
+    return pl.add(W_DIRECT, p, msk_conv1d_bwd_weight_ws(p));
 }
 
-// ---- one layer over several inputs (ms_conv1d_parts): a parts kernel where one applies, else part by part
-namespace {
+// p: the mirrored conv (make_convt)
+Plan convt_plan(const ms_convt1d_desc* d, const ConvP& p, int which) {
+    Plan pl;
+    if (which == 0) {
+        if (mst_convt1_applicable(p)) return pl.add(TF_THIN, p);            // one output channel: a stream
+        if (mss_convt_applicable(d)) pl.add(TF_LANES, p, 0, UNSUPPORTED);    // inference batch: a weight stream
+        if (msm_convt_fwd_applicable(p)) return pl.add(TF_MFMA, p, msm_convt_fwd_ws(p));
+        ConvP q = p;     // direct path: the loader modifier kind rides in q.act, the epilogue gets p.act
+        q.act = p.in_act ? MS_MOD_LRELU_FWD : MS_ACT_NONE;
+        return pl.add(TF_DIRECT, q);
+    }
+    if (which == 1) {
+        if (msm_convt_bwd_applicable(p)) return pl.add(TD_MFMA, p, msm_convt_bwd_data_ws(p));
+        ConvP q = p;
+        q.act = MS_ACT_NONE;
+        if (msm_fwd_applicable(q)) return pl.add(TD_CONV_MFMA, q, msm_fwd_ws(q));
+        return pl.add(TD_CONV_DIRECT, q);
+    }
+    // (every weight-gradient route also leaves the bias gradient's slice partials room at the workspace's tail;
+    //  the first three routes exclude each other)
+    const size_t tail = msk_channel_sum_ws(p.Cin) + 32;
+    if (mst_convt1_applicable(p)) pl.add(TW_THIN, p, mst_convt1_wgrad_ws(p) + tail, SHORT_WS);
+    if (mswt8_applicable(p)) pl.add(TW_8, p, mswt8_ws(p) + tail, SHORT_WS | UNSUPPORTED);
+    if (mswt2s_applicable(p)) pl.add(TW_2S, p, mswt2s_ws(p) + tail, SHORT_WS | UNSUPPORTED);
+    if (msm_convt_bwd_applicable(p)) return pl.add(TW_MFMA, p, msm_convt_bwd_weight_ws(p) + tail);
+    if (msm_bwd_weight_applicable(p)) return pl.add(TW_CONV_MFMA, p, msm_bwd_weight_ws(p) + tail);
+    return pl.add(TW_CONV_DIRECT, p, msk_conv1d_bwd_weight_ws(p) + tail);
+}
 
 bool parts_ok(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, ConvP* c) {
     if (!d || !parts || parts->count < 1 || parts->count > MS_CONV_PARTS_MAX) return false;
@@ -377,43 +383,214 @@ ms_conv1d_desc part_desc(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, 
     return di;
 }
 
-// 1: a parts kernel takes the call; 0: part by part
-int parts_kernel(const ConvP& c, const ms_conv1d_parts* parts, int which, bool with_image) {
-    if (parts->count < 2 || c.in_act) return 0;
-    if (msd_parts_applicable(c, parts, which) || msg4_parts_applicable(c, parts)) return 1;
-    if (which == 0) return (with_image && ms5_parts_applicable(c, parts, false)) || msg3_parts_fwd_applicable(c, parts);
-    if (which == 1) return (with_image && ms5_parts_applicable(c, parts, true)) || msg3_parts_bwd_data_applicable(c, parts);
-    return msw5_parts_applicable(c, parts) || msg3_parts_bwd_weight_applicable(c, parts);
+// c: the first part's conv (parts_ok); w, image: the call has the weights / a weight image
+Plan parts_plan(const ms_conv1d_desc* d, const ConvP& c, const ms_conv1d_parts* parts, int which, bool w, bool image) {
+    Plan pl;
+    if (parts->count >= 2 && !c.in_act) {
+        if (w && msd_parts_applicable(c, parts, which))
+            return pl.add(P_DISC, c, which == 2 ? msd_parts_bwd_weight_ws(c, parts) : 0);
+        if (w && msg4_parts_applicable(c, parts)) return pl.add(P_G4, c);
+        if (which == 2 && msw5_parts_applicable(c, parts)) return pl.add(P_K5, c, msw5_parts_ws(c, parts));
+        if (which < 2 && image && ms5_parts_applicable(c, parts, which == 1))
+            return pl.add(P_K5_IMG, c, ms5_parts_ws(c, parts, which == 1));
+        if (which == 0 && w && msg3_parts_fwd_applicable(c, parts)) return pl.add(P_G3, c);
+        if (which == 1 && w && msg3_parts_bwd_data_applicable(c, parts)) return pl.add(P_G3, c);
+        if (which == 2 && msg3_parts_bwd_weight_applicable(c, parts)) return pl.add(P_G3, c, msg3_parts_bwd_weight_ws(c, parts));
+    }
+    size_t n = 0;
+    for (int i = 0; i < parts->count; ++i) {
+        const ms_conv1d_desc di = part_desc(d, parts, i);
+        const size_t m = image && which < 2 && ms_conv1d_img_bytes(&di) ? ms_conv1d_img_workspace_bytes(&di, which)
+                                                                        : ms_conv1d_workspace_bytes(&di, which);
+        if (m > n) n = m;
+    }
+    return pl.add(P_EACH, c, n);
+}
+
+const char* route_name(Kind k, const ConvP& g) {
+    switch (k) {
+        case F_THIN_SHORT: case F_THIN: return mst_fwd_name(g);
+        case F_SMALL: return mss_conv_name(g);
+        case F_PAD4: case F_MFMA: case TD_CONV_MFMA: return msm_fwd_name(g);
+        case F_G4: return msg4_parts_name(0);
+        case F_G3: return msg3_fwd_name(g);
+        case F_G: return msg_fwd_name(g);
+        case F_DIRECT: case TD_CONV_DIRECT: return msk_conv1d_fwd_direct_name(g);
+        case D_PAD4: case D_MFMA: return msm_bwd_data_name(g);
+        case D_G4: return msg4_parts_name(1);
+        case D_G3: return msg3_bwd_data_name(g);
+        case D_G: return msg_bwd_data_name(g);
+        case D_THIN: return mst_bwd_data_name(g);
+        case D_DIRECT: case TF_DIRECT: return msk_conv1d_bwd_data_direct_name(g);
+        case W_THIN: return mst_bwd_weight_name(g);
+        case W_SHORT: return msws_name(g);
+        case W_32: return msw32_name(g);
+        case W_K5: return msw5_name(g);
+        case W_ROWS: return msw_bwd_weight_name(g);
+        case W_MFMA: case TW_CONV_MFMA: return msm_bwd_weight_name(g);
+        case W_G4: return msg4_parts_name(2);
+        case W_G3: return msg3_bwd_weight_name(g);
+        case W_G: return msg_bwd_weight_name(g);
+        case W_DIRECT: case TW_CONV_DIRECT: return msk_conv1d_bwd_weight_direct_name(g);
+        case TF_THIN: return mst_convt1_fwd_name();
+        case TF_LANES: return mss_convt_name(g.stride);
+        case TF_MFMA: return msm_convt_fwd_name(g);
+        case TD_MFMA: return msm_convt_bwd_data_name(g);
+        case TW_THIN: return mst_convt1_wgrad_name();
+        case TW_8: return mswt8_name(g);
+        case TW_2S: return mswt2s_name(g);
+        case TW_MFMA: return msm_convt_bwd_weight_name(g);
+        default: return "";            // (the parts launchers note their own kernels)
+    }
+}
+
+// Runs the plan: launch(kind, geometry) starts one route and returns its status.  In a profile session every route is noted before
+// it launches; the launchers of the templated families then overwrite the note with their exact instantiation.
+template <class Launch>
+int run(const Plan& pl, const void* ws, size_t ws_bytes, Launch launch) {
+    for (int i = 0; i < pl.n; ++i) {
+        const Route& r = pl.r[i];
+        if ((r.declines & SHORT_WS) && (!ws || ws_bytes < r.ws)) continue;
+        if ((r.declines & ALIGNED_WS) && (((uintptr_t)ws) & 15)) continue;
+        if (ms_prof_on()) ms_note_kernel(0, "%s", route_name(r.kind, r.g));
+        const int rc = launch(r.kind, r.g);
+        if (rc != MS_ERR_UNSUPPORTED || !(r.declines & UNSUPPORTED)) return rc;
+    }
+    return MS_ERR_UNSUPPORTED;           // (no route: the backward data of a strided or grouped reflection-padded conv)
 }
 
 }  // namespace
 
+extern "C" {
+
+int ms_conv1d_fwd(const ms_conv1d_desc* d, const float* x, const float* w, const float* bias,
+                  const float* residual, float* y, float* y_act, void* workspace,
+                  size_t workspace_bytes, ms_stream_t stream) {
+    ConvP p;
+    if (!make_conv(d, &p) || !x || !w || !y) return MS_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    // activation in front of the conv: applied to x on load (operand modifier "LeakyReLU of the value")
+    const float* xa = p.in_act ? x : nullptr;
+    const int xk = p.in_act ? MS_MOD_LRELU_FWD : 0;
+    return run(conv_plan(p, 0, residual, y_act), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
+        switch (k) {
+            case F_THIN_SHORT: case F_THIN: return mst_conv1d_fwd(g, x, w, bias, residual, y, s);
+            case F_SMALL: return mss_conv_fwd(g, x, w, bias, y, s);
+            case F_PAD4: {                // x and y in rows padded to g.Lin, then the padded problem's own workspace
+                const size_t xb = pad4_bytes(g, p.Cin), yb = pad4_bytes(g, p.Cout);
+                float* xp = (float*)workspace;
+                float* yp = (float*)((char*)workspace + xb);
+                int rc = pad_rows(x, xp, (size_t)p.B * p.Cin, p.Lin, g.Lin, s);
+                if (rc == MS_OK)
+                    rc = msm_conv1d_fwd(g, xp, nullptr, 0, w, bias, nullptr, yp, nullptr, (char*)workspace + xb + yb,
+                                        workspace_bytes - xb - yb, s);
+                if (rc == MS_OK) rc = unpad_rows(yp, nullptr, y, (size_t)p.B * p.Cout, p.Lin, g.Lin, s);
+                return rc;
+            }
+            case F_MFMA: return msm_conv1d_fwd(g, x, xa, xk, w, bias, residual, y, y_act, workspace, workspace_bytes, s);
+            case F_G4: { const ms_conv1d_parts q = one_part(g, x, y); return msg4_parts_fwd(g, &q, w, bias, s); }
+            case F_G3: return msg3_conv1d_fwd(g, x, w, bias, y, s);
+            case F_G: return msg_conv1d_fwd(g, x, w, bias, y, s);
+            default: return msk_conv1d_fwd_direct(g, x, xa, xk, w, bias, residual, y, y_act, s);
+        }
+    });
+}
+
+int ms_conv1d_bwd_data(const ms_conv1d_desc* d, const float* gy, const float* y_act,
+                       const float* w, const float* gx_add, float* gx, void* workspace,
+                       size_t workspace_bytes, ms_stream_t stream) {
+    ConvP p;
+    if (!make_conv(d, &p) || !gy || !w || !gx) return MS_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = run(conv_plan(p, 1, false, y_act), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
+        switch (k) {
+            case D_PAD4: {                // gy (and y_act) and gx in rows padded to g.Lin, then the padded problem's workspace
+                const size_t gb = pad4_bytes(g, p.Cout), xb = pad4_bytes(g, p.Cin);
+                char* wsp = (char*)workspace;
+                float* gp = (float*)wsp; wsp += gb;
+                float* ap = nullptr;
+                if (y_act) { ap = (float*)wsp; wsp += gb; }
+                float* xp = (float*)wsp; wsp += xb;
+                int rc = pad_rows(gy, gp, (size_t)p.B * p.Cout, p.Lin, g.Lin, s);
+                if (rc == MS_OK && y_act) rc = pad_rows(y_act, ap, (size_t)p.B * p.Cout, p.Lin, g.Lin, s);
+                if (rc == MS_OK)
+                    rc = msm_conv1d_bwd_data(g, gp, ap, w, nullptr, xp, wsp, workspace_bytes - (size_t)(wsp - (char*)workspace), s);
+                if (rc == MS_OK) rc = unpad_rows(xp, gx_add, gx, (size_t)p.B * p.Cin, p.Lin, g.Lin, s);
+                return rc;
+            }
+            case D_MFMA: return msm_conv1d_bwd_data(g, gy, y_act, w, gx_add, gx, workspace, workspace_bytes, s);
+            case D_G4: {
+                const ms_conv1d_parts q = one_part(g, nullptr, nullptr, gy, y_act, gx_add, gx);
+                return msg4_parts_bwd_data(g, &q, w, s);
+            }
+            case D_G3: return msg3_conv1d_bwd_data(g, gy, y_act, w, gx_add, gx, s);
+            case D_G: return msg_conv1d_bwd_data(g, gy, y_act, w, gx_add, gx, s);
+            case D_THIN: return mst_conv1d_bwd_data(g, gy, y_act, w, gx_add, gx, s);
+            default: return msk_conv1d_bwd_data_direct(g, gy, y_act, w, nullptr, MS_ACT_NONE, gx_add, gx, s);
+        }
+    });
+    if (rc != MS_OK || p.pad_mode != MS_PAD_REFLECT) return rc;
+    p.pad_mode = MS_PAD_ZERO;
+    return msk_reflect_fold_bwd(p, gy, y_act, w, gx, s);
+}
+
+int ms_conv1d_bwd_weight(const ms_conv1d_desc* d, const float* x, const float* gy,
+                         const float* y_act, float* gw, float* gb, float beta, void* workspace,
+                         size_t workspace_bytes, ms_stream_t stream) {
+    ConvP p;
+    if (!make_conv(d, &p) || !x || !gy || !gw) return MS_ERR_INVALID_ARG;
+    if (beta != 0.f && beta != 1.f) return MS_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const float* xa = p.in_act ? x : nullptr;
+    const int xk = p.in_act ? MS_MOD_LRELU_FWD : 0;
+    return run(conv_plan(p, 2, false, false), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
+        switch (k) {
+            case W_THIN: return mst_conv1d_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_SHORT: return msws_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_32: return msw32_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_K5: return msw5_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_ROWS: return msw_conv1d_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_MFMA:
+                return msm_conv1d_bwd_weight(g, x, xa, xk, gy, y_act, g.act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_G4: {
+                const ms_conv1d_parts q = one_part(g, x, nullptr, gy, y_act);
+                return msg4_parts_bwd_weight(g, &q, gw, gb, beta, s);
+            }
+            case W_G3: return msg3_conv1d_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            case W_G: return msg_conv1d_bwd_weight(g, x, gy, y_act, gw, gb, beta, workspace, workspace_bytes, s);
+            default:
+                return msk_conv1d_bwd_weight_direct(g, x, xa, xk, gy, y_act, g.act, gw, gb, beta, workspace, workspace_bytes, s);
+        }
+    });
+}
+
+// The query has no residual or saved activation; a call with them may reach routes a plain call does not: the workspace
+// covers both.
+size_t ms_conv1d_workspace_bytes(const ms_conv1d_desc* d, int which) {
+    ConvP p;
+    if (!make_conv(d, &p) || which < 0 || which > 2) return 0;
+    const size_t a = conv_plan(p, which, false, false).ws(), b = conv_plan(p, which, true, true).ws();
+    return a > b ? a : b;
+}
+
+const char* ms_conv1d_kernel_name(const ms_conv1d_desc* d, int which) {
+    ConvP p;
+    if (!make_conv(d, &p) || which < 0 || which > 2) return "";
+    const Plan pl = conv_plan(p, which, false, false);
+    return pl.n ? route_name(pl.r[0].kind, pl.r[0].g) : "";
+}
+
+// ---- one layer over several inputs (ms_conv1d_parts): a parts kernel where one applies, else part by part
 int ms_conv1d_parts_launches(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, int which, int with_image) {
     ConvP c;
     if (!parts_ok(d, parts, &c) || which < 0 || which > 2) return MS_ERR_INVALID_ARG;
-    return parts_kernel(c, parts, which, with_image != 0) ? 1 : parts->count;
+    return parts_plan(d, c, parts, which, true, with_image != 0).r[0].kind == P_EACH ? parts->count : 1;
 }
 
 size_t ms_conv1d_parts_workspace_bytes(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, int which, int with_image) {
     ConvP c;
     if (!parts_ok(d, parts, &c) || which < 0 || which > 2) return 0;
-    if (parts_kernel(c, parts, which, with_image != 0)) {
-        if (msg4_parts_applicable(c, parts)) return 0;
-        if (which != 2) {
-            if (msd_parts_applicable(c, parts, which)) return 0;
-            return (with_image && ms5_parts_applicable(c, parts, which == 1)) ? ms5_parts_ws(c, parts, which == 1) : 0;
-        }
-        if (msd_parts_applicable(c, parts, which)) return msd_parts_bwd_weight_ws(c, parts);
-        return msw5_parts_applicable(c, parts) ? msw5_parts_ws(c, parts) : msg3_parts_bwd_weight_ws(c, parts);
-    }
-    size_t n = 0;
-    for (int i = 0; i < parts->count; ++i) {
-        const ms_conv1d_desc di = part_desc(d, parts, i);
-        size_t m = ms_conv1d_workspace_bytes(&di, which);
-        if (with_image && which < 2 && ms_conv1d_img_bytes(&di)) m = ms_conv1d_img_workspace_bytes(&di, which);
-        if (m > n) n = m;
-    }
-    return n;
+    return parts_plan(d, c, parts, which, true, with_image != 0).ws();
 }
 
 int ms_conv1d_parts_fwd(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, const float* w, const float* bias,
@@ -421,28 +598,25 @@ int ms_conv1d_parts_fwd(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, c
     ConvP c;
     if (!parts_ok(d, parts, &c) || (!w && !image)) return MS_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (parts->count >= 2 && !c.in_act) {
-        if (w && msd_parts_applicable(c, parts, 0)) {
-            const int rc = msd_parts_fwd(c, parts, w, bias, s);
-            if (rc != MS_ERR_UNSUPPORTED) return rc;
+    return run(parts_plan(d, c, parts, 0, w, image), workspace, workspace_bytes, [&](Kind k, const ConvP&) {
+        switch (k) {
+            case P_DISC: return msd_parts_fwd(c, parts, w, bias, s);
+            case P_G4: return msg4_parts_fwd(c, parts, w, bias, s);
+            case P_K5_IMG: return ms5_parts_fwd(c, parts, image, bias, workspace, workspace_bytes, s);
+            case P_G3: return msg3_parts_fwd(c, parts, w, bias, s);
+            default: break;
         }
-        if (w && msg4_parts_applicable(c, parts)) return msg4_parts_fwd(c, parts, w, bias, s);
-        if (image && ms5_parts_applicable(c, parts, false))
-            return ms5_parts_fwd(c, parts, image, bias, workspace, workspace_bytes, s);
-        if (w && msg3_parts_fwd_applicable(c, parts)) return msg3_parts_fwd(c, parts, w, bias, s);
-    }
-    for (int i = 0; i < parts->count; ++i) {
-        const ms_conv1d_desc di = part_desc(d, parts, i);
-        int rc;
-        if (image && ms_conv1d_img_bytes(&di))
-            rc = ms_conv1d_img_fwd(&di, parts->x[i], image, bias, parts->y[i], workspace, workspace_bytes, stream);
-        else if (w)
-            rc = ms_conv1d_fwd(&di, parts->x[i], w, bias, nullptr, parts->y[i], nullptr, workspace, workspace_bytes, stream);
-        else
-            rc = MS_ERR_UNSUPPORTED;
-        if (rc != MS_OK) return rc;
-    }
-    return MS_OK;
+        for (int i = 0; i < parts->count; ++i) {
+            const ms_conv1d_desc di = part_desc(d, parts, i);
+            int rc = MS_ERR_UNSUPPORTED;
+            if (image && ms_conv1d_img_bytes(&di))
+                rc = ms_conv1d_img_fwd(&di, parts->x[i], image, bias, parts->y[i], workspace, workspace_bytes, stream);
+            else if (w)
+                rc = ms_conv1d_fwd(&di, parts->x[i], w, bias, nullptr, parts->y[i], nullptr, workspace, workspace_bytes, stream);
+            if (rc != MS_OK) return rc;
+        }
+        return (int)MS_OK;
+    });
 }
 
 int ms_conv1d_parts_bwd_data(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, const float* w, const void* image_bwd,
@@ -450,54 +624,52 @@ int ms_conv1d_parts_bwd_data(const ms_conv1d_desc* d, const ms_conv1d_parts* par
     ConvP c;
     if (!parts_ok(d, parts, &c) || (!w && !image_bwd)) return MS_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (parts->count >= 2 && !c.in_act) {
-        if (w && msd_parts_applicable(c, parts, 1)) {
-            const int rc = msd_parts_bwd_data(c, parts, w, s);
-            if (rc != MS_ERR_UNSUPPORTED) return rc;
+    return run(parts_plan(d, c, parts, 1, w, image_bwd), workspace, workspace_bytes, [&](Kind k, const ConvP&) {
+        switch (k) {
+            case P_DISC: return msd_parts_bwd_data(c, parts, w, s);
+            case P_G4: return msg4_parts_bwd_data(c, parts, w, s);
+            case P_K5_IMG: return ms5_parts_bwd_data(c, parts, image_bwd, workspace, workspace_bytes, s);
+            case P_G3: return msg3_parts_bwd_data(c, parts, w, s);
+            default: break;
         }
-        if (w && msg4_parts_applicable(c, parts)) return msg4_parts_bwd_data(c, parts, w, s);
-        if (image_bwd && ms5_parts_applicable(c, parts, true))
-            return ms5_parts_bwd_data(c, parts, image_bwd, workspace, workspace_bytes, s);
-        if (w && msg3_parts_bwd_data_applicable(c, parts)) return msg3_parts_bwd_data(c, parts, w, s);
-    }
-    for (int i = 0; i < parts->count; ++i) {
-        const ms_conv1d_desc di = part_desc(d, parts, i);
-        const float* ya = d->act == MS_ACT_NONE ? nullptr : parts->y_act[i];
-        int rc;
-        if (image_bwd && ms_conv1d_img_bytes(&di))
-            rc = ms_conv1d_img_bwd_data(&di, parts->gy[i], ya, image_bwd, parts->gx_add[i], parts->gx[i], workspace,
-                                        workspace_bytes, stream);
-        else if (w)
-            rc = ms_conv1d_bwd_data(&di, parts->gy[i], ya, w, parts->gx_add[i], parts->gx[i], workspace, workspace_bytes, stream);
-        else
-            rc = MS_ERR_UNSUPPORTED;
-        if (rc != MS_OK) return rc;
-    }
-    return MS_OK;
+        for (int i = 0; i < parts->count; ++i) {
+            const ms_conv1d_desc di = part_desc(d, parts, i);
+            const float* ya = d->act == MS_ACT_NONE ? nullptr : parts->y_act[i];
+            int rc = MS_ERR_UNSUPPORTED;
+            if (image_bwd && ms_conv1d_img_bytes(&di))
+                rc = ms_conv1d_img_bwd_data(&di, parts->gy[i], ya, image_bwd, parts->gx_add[i], parts->gx[i], workspace,
+                                            workspace_bytes, stream);
+            else if (w)
+                rc = ms_conv1d_bwd_data(&di, parts->gy[i], ya, w, parts->gx_add[i], parts->gx[i], workspace, workspace_bytes,
+                                        stream);
+            if (rc != MS_OK) return rc;
+        }
+        return (int)MS_OK;
+    });
 }
 
 int ms_conv1d_parts_bwd_weight(const ms_conv1d_desc* d, const ms_conv1d_parts* parts, float* gw, float* gb, float beta,
                                void* workspace, size_t workspace_bytes, ms_stream_t stream) {
     ConvP c;
     if (!parts_ok(d, parts, &c) || !gw || (beta != 0.f && beta != 1.f)) return MS_ERR_INVALID_ARG;
-    if (parts->count >= 2 && !c.in_act && msd_parts_applicable(c, parts, 2)) {
-        const int rc = msd_parts_bwd_weight(c, parts, gw, gb, beta, workspace, workspace_bytes, (hipStream_t)stream);
-        if (rc != MS_ERR_UNSUPPORTED) return rc;
-    }
-    if (parts->count >= 2 && !c.in_act && msg4_parts_applicable(c, parts))
-        return msg4_parts_bwd_weight(c, parts, gw, gb, beta, (hipStream_t)stream);
-    if (parts->count >= 2 && !c.in_act && msw5_parts_applicable(c, parts))
-        return msw5_parts_bwd_weight(c, parts, gw, gb, beta, workspace, workspace_bytes, (hipStream_t)stream);
-    if (parts->count >= 2 && !c.in_act && msg3_parts_bwd_weight_applicable(c, parts))
-        return msg3_parts_bwd_weight(c, parts, gw, gb, beta, workspace, workspace_bytes, (hipStream_t)stream);
-    for (int i = 0; i < parts->count; ++i) {             // the parts' gradients accumulate in order on the one stream
-        const ms_conv1d_desc di = part_desc(d, parts, i);
-        const float* ya = d->act == MS_ACT_NONE ? nullptr : parts->y_act[i];
-        const int rc = ms_conv1d_bwd_weight(&di, parts->x[i], parts->gy[i], ya, gw, gb, i == 0 ? beta : 1.f, workspace,
-                                            workspace_bytes, stream);
-        if (rc != MS_OK) return rc;
-    }
-    return MS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    return run(parts_plan(d, c, parts, 2, true, false), workspace, workspace_bytes, [&](Kind k, const ConvP&) {
+        switch (k) {
+            case P_DISC: return msd_parts_bwd_weight(c, parts, gw, gb, beta, workspace, workspace_bytes, s);
+            case P_G4: return msg4_parts_bwd_weight(c, parts, gw, gb, beta, s);
+            case P_K5: return msw5_parts_bwd_weight(c, parts, gw, gb, beta, workspace, workspace_bytes, s);
+            case P_G3: return msg3_parts_bwd_weight(c, parts, gw, gb, beta, workspace, workspace_bytes, s);
+            default: break;
+        }
+        for (int i = 0; i < parts->count; ++i) {         // the parts' gradients accumulate in order on the one stream
+            const ms_conv1d_desc di = part_desc(d, parts, i);
+            const float* ya = d->act == MS_ACT_NONE ? nullptr : parts->y_act[i];
+            const int rc = ms_conv1d_bwd_weight(&di, parts->x[i], parts->gy[i], ya, gw, gb, i == 0 ? beta : 1.f, workspace,
+                                                workspace_bytes, stream);
+            if (rc != MS_OK) return rc;
+        }
+        return (int)MS_OK;
+    });
 }
 
 static int multi_convs(const ms_wgrad_multi_desc* d, ConvP* cs) {
@@ -548,8 +720,7 @@ int ms_conv1d_bwd_weight_multi(const ms_wgrad_multi_desc* d, void* workspace, si
 }
 
 int ms_residual_stack_signs_supported(const ms_stack_desc* d) {
-    const char* sw = getenv("MSYNTH_ATOM_SIGNS");                // tuning / test switch (0: the fp32 activations are saved)
-    if (sw && atoi(sw) == 0) return 0;
+    if (!ms_switch_on("MSYNTH_ATOM_SIGNS")) return 0;            // tuning / test switch (0: the fp32 activations are saved)
     if (!d || d->count < 1 || d->count > MS_STACK_MAX || 2 * d->count > MS_WGRAD_MULTI_MAX) return 0;
     ConvP cs[MS_WGRAD_MULTI_MAX];
     int n = 0;
@@ -564,122 +735,6 @@ int ms_residual_stack_signs_supported(const ms_stack_desc* d) {
     return (msw_multi_takes_signs(cs, n) || msw32_multi_takes_signs(cs, n)) ? 1 : 0;
 }
 
-size_t ms_conv1d_workspace_bytes(const ms_conv1d_desc* d, int which) {
-    ConvP p;
-    if (!make_conv(d, &p)) return 0;
-    if (which == 0) {
-        if (!msm_fwd_applicable(p)) return 0;
-        size_t n = msm_fwd_ws(p);
-        if (pad4_applicable(p)) {         // padded copies of x and y + the padded problem's own workspace
-            const ConvP q = pad4_conv(p);
-            const size_t m = pad4_bytes(q, p.Cin) + pad4_bytes(q, p.Cout) + msm_fwd_ws(q);
-            if (m > n) n = m;
-        }
-        return n;
-    }
-    if (which == 1) {
-        // (reflection padding runs the zero-padded backward + the edge fold, see ms_conv1d_bwd_data)
-        if (p.pad_mode == MS_PAD_REFLECT && p.stride == 1 && p.groups == 1) p.pad_mode = MS_PAD_ZERO;
-        if (!msm_bwd_data_applicable(p)) return 0;
-        size_t n = msm_bwd_data_ws(p);
-        if (pad4_applicable(p)) {         // padded copies of gy, y_act and gx + the padded problem's own workspace
-            const ConvP q = pad4_conv(p);
-            const size_t m = 2 * pad4_bytes(q, p.Cout) + pad4_bytes(q, p.Cin) + msm_bwd_data_ws(q);
-            if (m > n) n = m;
-        }
-        return n;
-    }
-    if (which == 2) {
-        if (mst_bwd_weight_applicable(p)) return mst_bwd_weight_ws(p);
-        if (msws_applicable(p)) {
-            const size_t a = msws_ws(p);
-            const size_t rest = msm_bwd_weight_applicable(p) ? msm_bwd_weight_ws(p) : msk_conv1d_bwd_weight_ws(p);
-            return a > rest ? a : rest;
-        }
-        if (msw32_applicable(p)) {
-            const size_t a32 = msw32_ws(p);
-            const size_t rest = msm_bwd_weight_applicable(p) ? msm_bwd_weight_ws(p) : msk_conv1d_bwd_weight_ws(p);
-            return a32 > rest ? a32 : rest;
-        }
-        if (msw_bwd_weight_applicable(p)) {
-            size_t a = msw_bwd_weight_ws(p);
-            if (msw5_applicable(p) && msw5_ws(p) > a) a = msw5_ws(p);
-            const size_t rest = msm_bwd_weight_applicable(p) ? msm_bwd_weight_ws(p)
-                                : (msg_bwd_weight_applicable(p) ? msg_bwd_weight_ws(p) : msk_conv1d_bwd_weight_ws(p));
-            return a > rest ? a : rest;
-        }
-        return msm_bwd_weight_applicable(p) ? msm_bwd_weight_ws(p)
-               : (msg_bwd_weight_applicable(p) ? msg_bwd_weight_ws(p) : msk_conv1d_bwd_weight_ws(p));
-    }
-    return 0;
-}
-
-const char* ms_conv1d_kernel_name(const ms_conv1d_desc* d, int which) {
-    ConvP p;
-    if (!make_conv(d, &p)) return "";
-    if (which == 0 && mst_fwd_short_applicable(p)) return mst_fwd_name(p);
-    if (which == 0 && mss_conv_applicable(p)) return mss_conv_name(p);
-    // (rows padded to a multiple of 4, see pad4_applicable: the kernel of the padded problem)
-    if (which == 0 && msm_fwd_applicable(p) && pad4_applicable(p)) return msm_fwd_name(pad4_conv(p));
-    if (which == 1 && msm_bwd_data_applicable(p) && pad4_applicable(p)) return msm_bwd_data_name(pad4_conv(p));
-    if (!p.in_act && !msm_fwd_applicable(p)) {
-        const ms_conv1d_parts q = one_part(p);
-        if (msg4_parts_applicable(p, &q)) return which == 0 ? "k_g4_fwd" : (which == 1 ? "k_g4_bwd_data" : "k_g4_wgrad");
-    }
-    if (which == 0)
-        return msm_fwd_applicable(p) ? msm_fwd_name(p)
-               : (msg3_fwd_applicable(p) ? msg3_fwd_name(p)
-                  : msg_fwd_applicable(p) ? msg_fwd_name(p)
-                  : (mst_fwd_applicable(p) ? mst_fwd_name(p) : msk_conv1d_fwd_direct_name(p)));
-    if (which == 1 && p.pad_mode == MS_PAD_REFLECT && p.stride == 1 && p.groups == 1) {
-        ConvP z = p;
-        z.pad_mode = MS_PAD_ZERO;       // zero-padded backward + edge fold
-        if (msm_bwd_data_applicable(z)) return msm_bwd_data_name(z);
-    }
-    if (which == 1)
-        return msm_bwd_data_applicable(p) ? msm_bwd_data_name(p)
-               : (msg3_bwd_data_applicable(p) ? msg3_bwd_data_name(p)
-                  : msg_bwd_data_applicable(p) ? msg_bwd_data_name(p)
-                  : (mst_bwd_data_applicable(p) && p.pad_mode == MS_PAD_ZERO ? mst_bwd_data_name(p)
-                                                                              : msk_conv1d_bwd_data_direct_name(p)));
-    if (which == 2 && mst_bwd_weight_applicable(p)) return mst_bwd_weight_name(p);
-    if (which == 2 && msws_applicable(p)) return "k_wgrad_short";
-    if (which == 2 && msw32_applicable(p)) return p.act == MS_ACT_LRELU ? "k_wgrad32<1>" : "k_wgrad32<0>";
-    if (which == 2 && msw5_applicable(p)) return msw5_name(p);
-    if (which == 2 && msw_bwd_weight_applicable(p)) return msw_bwd_weight_name(p);
-    if (which == 2)
-        return msm_bwd_weight_applicable(p) ? msm_bwd_weight_name(p)
-               : (msg3_bwd_weight_applicable(p) ? msg3_bwd_weight_name(p)
-                  : msg_bwd_weight_applicable(p) ? msg_bwd_weight_name(p) : msk_conv1d_bwd_weight_direct_name(p));
-    return "";
-}
-
-const char* ms_convt1d_kernel_name(const ms_convt1d_desc* d, int which) {
-    ConvP p;
-    if (!make_convt(d, &p)) return "";
-    if (which == 0 && mst_convt1_applicable(p)) return mst_convt1_fwd_name();
-    if (which == 0 && mss_convt_applicable(d)) return mss_convt_name(d);
-    if (which == 2 && mst_convt1_applicable(p)) return mst_convt1_wgrad_name();
-    if (which == 0) return msm_convt_fwd_applicable(p) ? msm_convt_fwd_name(p) : msk_conv1d_bwd_data_direct_name(p);
-    if (which == 1) {
-        if (msm_convt_bwd_applicable(p)) return msm_convt_bwd_data_name(p);
-        ConvP q = p;
-        q.act = MS_ACT_NONE;
-        return msm_fwd_applicable(q) ? msm_fwd_name(q) : msk_conv1d_fwd_direct_name(q);
-    }
-    if (which == 2) {
-        if (mswt8_applicable(p)) return mswt8_name(p);
-        if (mswt2s_applicable(p)) return mswt2s_name(p);
-        if (msm_convt_bwd_applicable(p)) return msm_convt_bwd_weight_name(p);
-        return msm_bwd_weight_applicable(p) ? msm_bwd_weight_name(p) : msk_conv1d_bwd_weight_direct_name(p);
-    }
-    return "";
-}
-
-int ms_convt1d_out_len(const ms_convt1d_desc* d) {
-    ConvP p;
-    return make_convt(d, &p) ? p.Lin : MS_ERR_INVALID_ARG;
-}
 
 // y = act(bias + conv_transpose(x, w)) == backward-data of the mirrored conv, with epilogue
 int ms_convt1d_fwd(const ms_convt1d_desc* d, const float* x, const float* w, const float* bias,
@@ -687,16 +742,14 @@ int ms_convt1d_fwd(const ms_convt1d_desc* d, const float* x, const float* w, con
     ConvP p;
     if (!make_convt(d, &p) || !x || !w || !y) return MS_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (mst_convt1_applicable(p)) return mst_convt1_fwd(p, x, w, bias, y, s);      // one output channel: a stream
-    if (mss_convt_applicable(d)) {                                                 // inference batch: a weight stream
-        const int rc = mss_convt_fwd(d, x, w, bias, y, s);
-        if (rc != MS_ERR_UNSUPPORTED) return rc;
-    }
-    if (msm_convt_fwd_applicable(p))
-        return msm_convt1d_fwd(p, x, w, bias, y, workspace, workspace_bytes, s);
-    ConvP q = p;     // direct path: the loader modifier kind rides in q.act, the epilogue gets p.act
-    q.act = p.in_act ? MS_MOD_LRELU_FWD : MS_ACT_NONE;
-    return msk_conv1d_bwd_data_direct(q, x, p.in_act ? x : nullptr, w, bias, p.act, nullptr, y, s);
+    return run(convt_plan(d, p, 0), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
+        switch (k) {
+            case TF_THIN: return mst_convt1_fwd(g, x, w, bias, y, s);
+            case TF_LANES: return mss_convt_fwd(d, x, w, bias, y, s);
+            case TF_MFMA: return msm_convt1d_fwd(g, x, w, bias, y, workspace, workspace_bytes, s);
+            default: return msk_conv1d_bwd_data_direct(g, x, p.in_act ? x : nullptr, w, bias, p.act, nullptr, y, s);
+        }
+    });
 }
 
 // gx = conv(gy * act'(y_act), w) with the mirrored conv geometry (no bias / activation)
@@ -706,14 +759,14 @@ int ms_convt1d_bwd_data(const ms_convt1d_desc* d, const float* gy, const float* 
     ConvP p;
     if (!make_convt(d, &p) || !gy || !w || !gx) return MS_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (msm_convt_bwd_applicable(p))
-        return msm_convt1d_bwd_data(p, gy, y_act, w, gx, workspace, workspace_bytes, s);
-    ConvP q = p;
-    q.act = MS_ACT_NONE;
-    if (msm_fwd_applicable(q))
-        return msm_conv1d_fwd(q, gy, y_act, p.act, w, nullptr, nullptr, gx, nullptr, workspace,
-                              workspace_bytes, s);
-    return msk_conv1d_fwd_direct(q, gy, y_act, p.act, w, nullptr, nullptr, gx, nullptr, s);
+    return run(convt_plan(d, p, 1), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
+        switch (k) {
+            case TD_MFMA: return msm_convt1d_bwd_data(g, gy, y_act, w, gx, workspace, workspace_bytes, s);
+            case TD_CONV_MFMA:
+                return msm_conv1d_fwd(g, gy, y_act, p.act, w, nullptr, nullptr, gx, nullptr, workspace, workspace_bytes, s);
+            default: return msk_conv1d_fwd_direct(g, gy, y_act, p.act, w, nullptr, nullptr, gx, nullptr, s);
+        }
+    });
 }
 
 // gw[ci_T, co_T, k] = sum x[b,ci_T,i] * gp[b,co_T,i*stride - pad + k]: the mirrored conv's weight
@@ -725,24 +778,21 @@ int ms_convt1d_bwd_weight(const ms_convt1d_desc* d, const float* x, const float*
     if (!make_convt(d, &p) || !x || !gy || !gw) return MS_ERR_INVALID_ARG;
     if (beta != 0.f && beta != 1.f) return MS_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    int rc = MS_ERR_UNSUPPORTED;
-    if (mst_convt1_applicable(p) && workspace && workspace_bytes >= mst_convt1_wgrad_ws(p) + msk_channel_sum_ws(p.Cin) + 32)
-        rc = mst_convt1_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
-    else if (mswt8_applicable(p) && workspace && workspace_bytes >= mswt8_ws(p) + msk_channel_sum_ws(p.Cin) + 32)
-        rc = mswt8_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
-    else if (mswt2s_applicable(p) && workspace && workspace_bytes >= mswt2s_ws(p) + msk_channel_sum_ws(p.Cin) + 32)
-        rc = mswt2s_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
-    if (rc != MS_ERR_UNSUPPORTED) {
-    } else if (msm_convt_bwd_applicable(p))
-        rc = msm_convt1d_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
-    else if (msm_bwd_weight_applicable(p))
-        rc = msm_conv1d_bwd_weight(p, gy, y_act, p.act, x, p.in_act ? x : nullptr,
-                                   p.in_act ? MS_MOD_LRELU_FWD : 0, gw, nullptr, beta, workspace,
-                                   workspace_bytes, s);
-    else
-        rc = msk_conv1d_bwd_weight_direct(p, gy, y_act, p.act, x, p.in_act ? x : nullptr,
-                                          p.in_act ? MS_MOD_LRELU_FWD : 0, gw, nullptr, beta,
-                                          workspace, workspace_bytes, s);
+    const float* xa = p.in_act ? x : nullptr;
+    const int xk = p.in_act ? MS_MOD_LRELU_FWD : 0;
+    const int rc = run(convt_plan(d, p, 2), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
+        switch (k) {
+            case TW_THIN: return mst_convt1_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
+            case TW_8: return mswt8_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
+            case TW_2S: return mswt2s_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
+            case TW_MFMA: return msm_convt1d_bwd_weight(p, x, gy, y_act, gw, beta, workspace, workspace_bytes, s);
+            case TW_CONV_MFMA:
+                return msm_conv1d_bwd_weight(p, gy, y_act, p.act, x, xa, xk, gw, nullptr, beta, workspace, workspace_bytes, s);
+            default:
+                return msk_conv1d_bwd_weight_direct(p, gy, y_act, p.act, x, xa, xk, gw, nullptr, beta, workspace,
+                                                    workspace_bytes, s);
+        }
+    });
     if (rc != MS_OK) return rc;
     if (gb) {   // bias grad: the slice partials live at the tail of the workspace
         const size_t tail = msk_channel_sum_ws(p.Cin);
@@ -757,25 +807,12 @@ int ms_convt1d_bwd_weight(const ms_convt1d_desc* d, const float* x, const float*
 
 size_t ms_convt1d_workspace_bytes(const ms_convt1d_desc* d, int which) {
     ConvP p;
-    if (!make_convt(d, &p)) return 0;
-    if (which == 0) return msm_convt_fwd_applicable(p) ? msm_convt_fwd_ws(p) : 0;
-    if (which == 1) {
-        if (msm_convt_bwd_applicable(p)) return msm_convt_bwd_data_ws(p);
-        ConvP q = p;
-        q.act = MS_ACT_NONE;
-        return msm_fwd_applicable(q) ? msm_fwd_ws(q) : 0;
-    }
-    if (which == 2) {
-        const size_t tail = msk_channel_sum_ws(p.Cin) + 32;   // bias-grad slice partials
-        size_t t8 = mswt8_applicable(p) ? mswt8_ws(p) : 0;
-        if (mst_convt1_applicable(p) && mst_convt1_wgrad_ws(p) > t8) t8 = mst_convt1_wgrad_ws(p);
-        if (mswt2s_applicable(p) && mswt2s_ws(p) > t8) t8 = mswt2s_ws(p);
-        size_t n = msm_convt_bwd_applicable(p) ? msm_convt_bwd_weight_ws(p)
-                   : (msm_bwd_weight_applicable(p) ? msm_bwd_weight_ws(p) : msk_conv1d_bwd_weight_ws(p));
-        if (t8 > n) n = t8;
-        return n + tail;
-    }
-    return 0;
+    return make_convt(d, &p) && which >= 0 && which <= 2 ? convt_plan(d, p, which).ws() : 0;
+}
+
+const char* ms_convt1d_kernel_name(const ms_convt1d_desc* d, int which) {
+    ConvP p;
+    return make_convt(d, &p) && which >= 0 && which <= 2 ? route_name(convt_plan(d, p, which).r[0].kind, p) : "";
 }
 
 }  // extern "C"

@@ -690,7 +690,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_atom_fwd(AtomP p, const float* _
 // pieces per operand element: 2 (block-scaled fp16 x 2, three products) unless MSYNTH_ATOM_NP=3 (bf16 x 3, six products:
 // the r03 kernel, bitwise equal to the two row-tile launches)
 int atom_np() {
-    static const int np = (getenv("MSYNTH_ATOM_NP") && atoi(getenv("MSYNTH_ATOM_NP")) == 3) ? 3 : 2;
+    static const int np = ms_switch_int("MSYNTH_ATOM_NP", 2) == 3 ? 3 : 2;      // read once: ms_common.h
     return np;
 }
 
@@ -795,8 +795,7 @@ size_t ms_residual_atom_image_bytes(int32_t C) {
 }
 
 int ms_residual_atom_supported(const ms_atom_desc* d) {
-    const char* sw = getenv("MSYNTH_ATOM");                      // tuning / test switch (0: the two row-tile launches)
-    if (sw && atoi(sw) == 0) return 0;
+    if (!ms_switch_on("MSYNTH_ATOM")) return 0;                  // tuning / test switch (0: the two row-tile launches)
     return atom_ok(d) ? 1 : 0;
 }
 
@@ -867,8 +866,7 @@ int ms_residual_atom_bwd_data_signs(const ms_atom_desc* d, const float* gy, cons
 
 int ms_residual_atom_bwd_supported(const ms_atom_desc* d) {
     if (!ms_residual_atom_supported(d)) return 0;
-    const char* sw = getenv("MSYNTH_ATOM_BWD");                  // tuning / test switch (0: the two backward-data launches)
-    if (sw && atoi(sw) == 0) return 0;
+    if (!ms_switch_on("MSYNTH_ATOM_BWD")) return 0;              // tuning / test switch (0: the two backward-data launches)
     // (a tile yields NTP - 2 dil output columns: with 64-column tiles (128 / 256 channels) dilation 9 spends 28 % of both
     //  GEMMs on halo.  With six products per multiply that lost against the two row-tile launches; with three it wins:
     //  B = 32: 89 vs 114 us at 128 channels, 41 vs 69 us at 256 -- r04 takes every atom of the generator.)

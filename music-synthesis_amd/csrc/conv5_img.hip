@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) void k_conv5_finish(const float* __restrict__ 
 
 // pieces per operand element: 2 (block-scaled fp16 x 2, three products) unless MSYNTH_C5_NP=3 (bf16 x 3, six products)
 int c5_np() {
-    static const int np = (getenv("MSYNTH_C5_NP") && atoi(getenv("MSYNTH_C5_NP")) == 3) ? 3 : 2;
+    static const int np = ms_switch_int("MSYNTH_C5_NP", 2) == 3 ? 3 : 2;      // read once: ms_common.h
     return np;
 }
 
@@ -675,8 +675,7 @@ bool c5_geometry(const ConvP& c, bool backward, C5P* p) {
 }
 
 bool c5_enabled() {
-    const char* sw = getenv("MSYNTH_CONV5IMG");               // tuning / test switch (0: the generic row kernels)
-    return !(sw && atoi(sw) == 0);
+    return ms_switch_on("MSYNTH_CONV5IMG");                   // tuning / test switch (0: the generic row kernels)
 }
 
 template <int MODE, int NP>
@@ -761,8 +760,7 @@ size_t c5_pre_bytes(const C5P& p, const C5Parts& q, size_t* offP, size_t* offS, 
 }
 
 bool c5_pre_enabled() {
-    const char* sw = getenv("MSYNTH_C5_PRE");                 // tuning / test switch (0: operands split inside the K loop)
-    return c5_np() == 2 && !(sw && atoi(sw) == 0);
+    return c5_np() == 2 && ms_switch_on("MSYNTH_C5_PRE");     // tuning / test switch (0: operands split inside the K loop)
 }
 
 template <int MODE, int NP, bool PRE>

@@ -1103,8 +1103,7 @@ RowCfg pick_row_cfg(int M, int B, int L, bool dense = false) {
     if (M <= 32) return ROW_32x256;
     if (L < 128) return (M >= 512 && (long long)B * L >= 512) ? ROW_64x128 : ROW_64x64;   // short rows: R = 128 / L rows per tile
     const long long N = (long long)B * L;
-    const char* r3 = getenv("MSYNTH_ROWS3");
-    const bool split = dense && L % 4 == 0 && !(r3 && atoi(r3) == 0);
+    const bool split = dense && L % 4 == 0 && ms_switch_on("MSYNTH_ROWS3");
     if (M >= 128 && (N / 128) * (M / 128) >= 384 && !split) return ROW_128x128;
     if ((N / 128) * (M / 64) < 192) return ROW_64x64;   // small batches: more, smaller workgroups
     return ROW_64x128;
@@ -1361,8 +1360,7 @@ int rows_wgs(RowCfg cfg, const RowP& p) {
 }
 
 int split_max_wgs() {
-    const char* e = getenv("MSYNTH_SPLIT_WGS");   // tuning / test switch (0 disables split-K)
-    return e ? atoi(e) : 192;
+    return ms_switch_int("MSYNTH_SPLIT_WGS", 192);   // tuning / test switch (0 disables split-K)
 }
 
 RowSplit plan_rows_split(RowCfg cfg, const RowP& p, int CC) {

@@ -491,8 +491,7 @@ int launch_tile(int tile, const Row2P& p, const float* X, const float* Xact, con
 }  // namespace
 
 bool msr2_supported(int tile, int K, int CC, int act_mode, int epi_s, const Row2P& p, int in_s) {
-    const char* e = getenv("MSYNTH_ROWS2");            // tuning / test switch (0 disables)
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_ROWS2")) return false;       // tuning / test switch (0 disables)
     if (tile < 0 || tile > MSR2_32x256) return false;
     if (act_mode < 0 || act_mode > 3) return false;
     if (in_s == 0) {      // short-row mode: R whole rows of any length per tile (the 1024 -> 1024 k5 conv at L = 17 / 9)

@@ -837,8 +837,7 @@ int launch_tile(int tile, const Row2P& p, const float* X, const float* Xact, con
 // Same contract as msr2_supported / msr2_launch (conv_rows2.h) for the subset: stride-1 plain rows
 // (in_s == 1), zero padding, L % 4 == 0, K in {3, 5}, chunks of 16 channels, act_mode 0 / 1, plain epilogue.
 bool msr3_supported(int tile, int K, int act_mode, int epi_s, const Row2P& p, int in_s) {
-    const char* sw = getenv("MSYNTH_ROWS3");         // tuning / test switch (0: stay on the fp32-MFMA kernels)
-    if (sw && atoi(sw) == 0) return false;
+    if (!ms_switch_on("MSYNTH_ROWS3")) return false;     // tuning / test switch (0: stay on the fp32-MFMA kernels)
     if (tile < 0 || tile >= MSR2_32x256) return false;      // (32 x 256: measured no faster than the fp32 kernel)
     if (in_s != 1 || epi_s != 0 || (act_mode != 0 && act_mode != 1)) return false;
     if (K != 3 && K != 5) return false;
@@ -869,8 +868,7 @@ int msr3_launch(int tile, int K, int act_mode, const Row2P& p, const float* X, c
 // Paired eight-wave form (k_conv_rows3p): bm = 128 (K = 3) or 64 rows x two adjacent 128-column tiles per
 // workgroup.  The caller uses it where the grid still fills the chip: msr3p_grid gives the workgroup count.
 bool msr3p_supported(int bm, int K, int act_mode, int epi_s, const Row2P& p, int in_s) {
-    const char* sw = getenv("MSYNTH_ROWS3P");        // tuning / test switch (0: four-wave kernel only)
-    if (sw && atoi(sw) == 0) return false;
+    if (!ms_switch_on("MSYNTH_ROWS3P")) return false;    // tuning / test switch (0: four-wave kernel only)
     if (bm != 32 && bm != 64 && bm != 128) return false;
     if (!msr3_supported(bm == 128 ? MSR2_128x128 : MSR2_64x128, K, act_mode, epi_s, p, in_s)) return false;
     if (!rows_vec(p)) return false;
@@ -906,10 +904,8 @@ int msr3p_launch(int bm, int K, int act_mode, const Row2P& p, const float* X, co
 // Transposed-conv forward on the paired kernel (HS form).  p: the row description of the mirrored conv with the
 // 3-column window (rows2_pick(.., K = 2, ..)), p.M = Cout * S GEMM rows, p.KG = 2 CK; W packed by k_pack_convt_w2.
 bool msr3p_convt_supported(int bm, int S, const Row2P& p) {
-    const char* sw = getenv("MSYNTH_ROWS3P");
-    if (sw && atoi(sw) == 0) return false;
-    const char* sc = getenv("MSYNTH_CONVT3");        // tuning / test switch (0: fp32-MFMA transposed-conv kernel)
-    if (sc && atoi(sc) == 0) return false;
+    if (!ms_switch_on("MSYNTH_ROWS3P")) return false;
+    if (!ms_switch_on("MSYNTH_CONVT3")) return false;    // tuning / test switch (0: fp32-MFMA transposed-conv kernel)
     if ((S != 2 && S != 8) || (bm != 64 && bm != 128)) return false;
     if (p.M % 64 || p.CK % CC3 || p.CKs % CC3 || p.dil != 1 || p.off0 != -1) return false;
     if (!rows_vec(p) || (long long)p.B * (p.M / S) * p.L * S >= (1ll << 31)) return false;

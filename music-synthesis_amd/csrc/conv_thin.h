@@ -34,5 +34,5 @@ bool mss_conv_applicable(const ConvP& p);
 const char* mss_conv_name(const ConvP& p);
 int mss_conv_fwd(const ConvP& p, const float* x, const float* w, const float* bias, float* y, hipStream_t s);
 bool mss_convt_applicable(const ms_convt1d_desc* d);
-const char* mss_convt_name(const ms_convt1d_desc* d);
+const char* mss_convt_name(int stride);
 int mss_convt_fwd(const ms_convt1d_desc* d, const float* x, const float* w, const float* bias, float* y, hipStream_t s);

@@ -645,8 +645,7 @@ int convt1_lines_per_wg(const ConvP& p) { return ms_ceil_div(p.B, 512); }
 }  // namespace
 
 bool mst_convt1_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_CONVT1");          // tuning / test switch (0: direct kernels)
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_CONVT1")) return false;     // tuning / test switch (0: direct kernels)
     return convt1_geom(p);
 }
 const char* mst_convt1_fwd_name() { return "k_convt1_fwd"; }

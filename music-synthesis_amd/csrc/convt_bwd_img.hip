@@ -296,10 +296,7 @@ __global__ __launch_bounds__(256) void k_convt_bwd_finish(const f32x4* __restric
     }
 }
 
-bool cb_enabled() {
-    const char* sw = getenv("MSYNTH_CONVTBWDIMG");            // tuning / test switch (0: the fp32 row-tile kernels)
-    return !(sw && atoi(sw) == 0);
-}
+bool cb_enabled() { return ms_switch_on("MSYNTH_CONVTBWDIMG"); }   // tuning / test switch (0: the fp32 row-tile kernels)
 
 bool cb_geometry(const ms_convt1d_desc* d, CbP* p, int* tm) {
     if (!d || d->B <= 0 || d->Lin <= 0 || d->Cin <= 0 || d->Cout <= 0) return false;

@@ -267,8 +267,7 @@ bool cs_geometry(const ms_convt1d_desc* d, CsP* p) {
 
 // internal interface used by convt_img.hip's ms_convt1d_img_* entry points
 bool msct_short_ok(const ms_convt1d_desc* d) {
-    const char* sw = getenv("MSYNTH_CONVTSHORT");               // tuning / test switch (0: the generic row kernels)
-    if (sw && atoi(sw) == 0) return false;
+    if (!ms_switch_on("MSYNTH_CONVTSHORT")) return false;       // tuning / test switch (0: the generic row kernels)
     CsP p;
     return cs_geometry(d, &p);
 }

@@ -409,8 +409,7 @@ bool ct_ok(const ms_convt1d_desc* d) {
     // (r04, fp16 x 2 images, B = 32: stride 2 on this kernel 37.7 / 30.8 us against 40.0 / 28.0 on the row kernel -- a wash)
     if (d->stride != 8 || (long long)d->B * d->Lin < 1024) return false;
     if ((long long)d->B * d->Cin * d->Lin * 4 >= (1ll << 31) || (long long)d->B * d->Cout * d->Lin * d->stride * 4 >= (1ll << 31)) return false;
-    const char* sw = getenv("MSYNTH_CONVTIMG");                 // tuning / test switch (0: the row-tile kernels)
-    return !(sw && atoi(sw) == 0);
+    return ms_switch_on("MSYNTH_CONVTIMG");                     // tuning / test switch (0: the row-tile kernels)
 }
 
 }  // namespace

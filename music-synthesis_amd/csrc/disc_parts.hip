@@ -398,17 +398,17 @@ constexpr int JUDGE_SLABS = 48;          // batch slabs of the judge conv's weig
 }  // namespace
 
 bool msd_parts_applicable(const ConvP& c, const ms_conv1d_parts* parts, int which) {
-    const char* e = getenv("MSYNTH_DTHIN");                 // tuning / test switch (0: the per-scale kernels, part by part)
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_DTHIN")) return false;       // tuning / test switch (0: the per-scale kernels, part by part)
     if (!parts || parts->count < 1 || parts->count > NP) return false;
     if (is_first(c)) return true;
-    if (is_judge(c)) {
-        for (int i = 0; i < parts->count; ++i)
-            if (parts->Lin[i] > JL) return false;
-        return true;
+    if (!is_judge(c)) return false;
+    for (int i = 0; i < parts->count; ++i) {
+        if (parts->Lin[i] > JL) return false;
+        // the judge conv's kernels load 16 bytes at a time: x (forward, weight gradient) / gx and gx_add (backward data)
+        const uintptr_t a = which == 1 ? (uintptr_t)parts->gx[i] | (uintptr_t)parts->gx_add[i] : (uintptr_t)parts->x[i];
+        if (a & 15) return false;
     }
-    (void)which;
-    return false;
+    return true;
 }
 
 size_t msd_parts_bwd_weight_ws(const ConvP& c, const ms_conv1d_parts* parts) {
@@ -423,7 +423,6 @@ int msd_parts_fwd(const ConvP& c, const ms_conv1d_parts* parts, const float* w, 
     if (!table(c, parts, first ? FT : 0, first ? FC : c.Cin, &q)) return MS_ERR_INVALID_ARG;
     for (int i = 0; i < q.count; ++i) {
         if (!parts->x[i] || !parts->y[i]) return MS_ERR_INVALID_ARG;
-        if (!first && (((uintptr_t)parts->x[i]) & 15)) return MS_ERR_UNSUPPORTED;
         q.a[i] = parts->x[i]; q.o[i] = parts->y[i];
     }
     if (first) {
@@ -443,8 +442,6 @@ int msd_parts_bwd_data(const ConvP& c, const ms_conv1d_parts* parts, const float
     if (!table(c, parts, first ? 256 : 0, first ? FC : c.Cin, &q)) return MS_ERR_INVALID_ARG;
     for (int i = 0; i < q.count; ++i) {
         if (!parts->gy[i] || !parts->gx[i] || (first && !parts->y_act[i])) return MS_ERR_INVALID_ARG;
-        if (!first && ((((uintptr_t)parts->gx[i]) & 15) || (parts->gx_add[i] && (((uintptr_t)parts->gx_add[i]) & 15))))
-            return MS_ERR_UNSUPPORTED;
         q.a[i] = parts->gy[i]; q.b[i] = parts->y_act[i]; q.c[i] = parts->gx_add[i]; q.o[i] = parts->gx[i];
     }
     if (first) {
@@ -484,7 +481,6 @@ int msd_parts_bwd_weight(const ConvP& c, const ms_conv1d_parts* parts, float* gw
     } else {
         for (int i = 0; i < q.count; ++i) {
             if (!parts->x[i] || !parts->gy[i]) return MS_ERR_INVALID_ARG;
-            if (((uintptr_t)parts->x[i]) & 15) return MS_ERR_UNSUPPORTED;
             q.a[i] = parts->x[i]; q.b[i] = parts->gy[i];
         }
         const int rows = q.wg0[q.count], chunks = c.Cin / 256;

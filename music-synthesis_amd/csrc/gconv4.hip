@@ -456,10 +456,7 @@ __global__ __launch_bounds__(256) void k_g4_wgrad(G4Parts q, int C, int act, flo
     }
 }
 
-bool g4_enabled() {
-    const char* sw = getenv("MSYNTH_G4");        // tuning / test switch (0: the matrix-pipe kernels of gconv_split.hip)
-    return !(sw && atoi(sw) == 0);
-}
+bool g4_enabled() { return ms_switch_on("MSYNTH_G4"); }   // tuning / test switch (0: the matrix-pipe kernels of gconv_split.hip)
 
 bool g4_layer(const ConvP& c) {
     return c.groups >= 1 && c.Cg == CG && c.Og == CG && c.K == K4 && c.stride == 4 && c.pad == PAD4 && c.dil == 1 &&
@@ -504,6 +501,8 @@ bool msg4_parts_applicable(const ConvP& c, const ms_conv1d_parts* parts) {
     return g4_table(c, parts, &q);
 }
 
+const char* msg4_parts_name(int which) { return which == 0 ? "k_g4_fwd" : which == 1 ? "k_g4_bwd_data" : "k_g4_wgrad"; }
+
 int msg4_parts_fwd(const ConvP& c, const ms_conv1d_parts* parts, const float* w, const float* bias, hipStream_t s) {
     G4Parts q;
     if (!g4_table(c, parts, &q)) return MS_ERR_UNSUPPORTED;
@@ -512,7 +511,7 @@ int msg4_parts_fwd(const ConvP& c, const ms_conv1d_parts* parts, const float* w,
         if (!parts->x[i] || !parts->y[i]) return MS_ERR_INVALID_ARG;
         q.a[i] = parts->x[i]; q.o[i] = parts->y[i];
     }
-    ms_note_kernel(0, "k_g4_fwd");
+    ms_note_kernel(0, "%s", msg4_parts_name(0));
     hipLaunchKernelGGL(k_g4_fwd, dim3(q.wg0[q.count], c.groups), dim3(256), g4_rows_lds(q, 44), s, q, c.Cin, w, bias, c.act, c.slope);
     MS_CHECK_LAUNCH();
     return MS_OK;
@@ -527,7 +526,7 @@ int msg4_parts_bwd_data(const ConvP& c, const ms_conv1d_parts* parts, const floa
         q.a[i] = parts->gy[i]; q.b[i] = c.act != MS_ACT_NONE ? parts->y_act[i] : nullptr; q.c[i] = parts->gx_add[i];
         q.o[i] = parts->gx[i];
     }
-    ms_note_kernel(0, "k_g4_bwd_data");
+    ms_note_kernel(0, "%s", msg4_parts_name(1));
     hipLaunchKernelGGL(k_g4_bwd_data, dim3(q.wg0[q.count], c.groups), dim3(256), g4_rows_lds(q, 11), s, q, c.Cin, w, c.act, c.slope);
     MS_CHECK_LAUNCH();
     return MS_OK;
@@ -547,7 +546,7 @@ int msg4_parts_bwd_weight(const ConvP& c, const ms_conv1d_parts* parts, float* g
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_g4_wgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         ms_done_on_device(attr_set);
     }
-    ms_note_kernel(0, "k_g4_wgrad");
+    ms_note_kernel(0, "%s", msg4_parts_name(2));
     hipLaunchKernelGGL(k_g4_wgrad, dim3(c.groups), dim3(256), lds, s, q, c.Cin, c.act, c.slope, beta, gw, gb);
     MS_CHECK_LAUNCH();
     return MS_OK;

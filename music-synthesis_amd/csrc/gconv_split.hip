@@ -1029,9 +1029,7 @@ int pick_rb(int Lout) {
 }  // namespace
 
 bool msg3_fwd_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_GCONV3");          // read per call: the micro-benchmarks flip it
-    const bool on = !e || atoi(e) != 0;
-    return on && p.K == GK && p.stride == GS && p.Cg == GCG && p.dil == 1 && p.pad_mode == MS_PAD_ZERO &&
+    return ms_switch_on("MSYNTH_GCONV3") && p.K == GK && p.stride == GS && p.Cg == GCG && p.dil == 1 && p.pad_mode == MS_PAD_ZERO &&
            p.Og <= 16 && p.groups <= 65535 &&
            (p.act == MS_ACT_NONE || (p.act == MS_ACT_LRELU && p.slope >= 0.f && p.slope <= 1.f)) &&
            (long long)p.B * p.Cin * p.Lin * 4 < (1ll << 31) &&
@@ -1157,9 +1155,7 @@ int msg3_parts_fwd(const ConvP& c, const ms_conv1d_parts* parts, const float* w,
 }
 
 bool msg3_bwd_weight_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_GCONV3");
-    const bool on = !e || atoi(e) != 0;
-    return on && p.K == GK && p.stride == GS && p.Cg == GCG && p.dil == 1 && p.pad_mode == MS_PAD_ZERO &&
+    return ms_switch_on("MSYNTH_GCONV3") && p.K == GK && p.stride == GS && p.Cg == GCG && p.dil == 1 && p.pad_mode == MS_PAD_ZERO &&
            p.Og <= 16 && p.groups <= 65535 && (long long)p.B * p.Cin * p.Lin * 4 < (1ll << 30) &&
            (long long)p.B * p.Cout * p.Lout * 4 < (1ll << 31);
 }
@@ -1245,9 +1241,7 @@ int msg3_parts_bwd_weight(const ConvP& c, const ms_conv1d_parts* parts, float* g
 }
 
 bool msg3_bwd_data_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_GCONV3");
-    const bool on = !e || atoi(e) != 0;
-    return on && p.K == GK && p.stride == GS && p.Cg == GCG && p.dil == 1 && p.pad == 20 &&
+    return ms_switch_on("MSYNTH_GCONV3") && p.K == GK && p.stride == GS && p.Cg == GCG && p.dil == 1 && p.pad == 20 &&
            p.pad_mode == MS_PAD_ZERO && p.Og == 16 && p.groups <= 65535 &&
            (long long)p.B * p.Cout * p.Lout * 4 < (1ll << 31);
 }

@@ -2,9 +2,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "msynth.h"
 
 #define MS_WAVE 64
+
+// Tuning / test switches (MSYNTH_*, DESIGN_HISTORY.md "Tuning / test switches"): the only place the library reads its
+// environment.  Read on every call, so a test or a micro-benchmark can flip a switch inside one process -- except the four
+// that fix the layout of a packed weight image (MSYNTH_ATOM_NP, MSYNTH_C5_NP, MSYNTH_W5_NP, MSYNTH_WROWS3_NP): an image packed
+// under one value and launched under another would be read in the wrong layout, so their readers keep the first value.
+static inline int ms_switch_int(const char* name, int dflt) {    // the variable's integer value, dflt when unset
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static inline bool ms_switch_on(const char* name) { return ms_switch_int(name, 1) != 0; }   // on unless set to 0
 
 #define MS_CHECK_LAUNCH()                                   \
     do {                                                    \

@@ -203,10 +203,7 @@ __global__ __launch_bounds__(256) void k_conv_small(const ConvP p, const float* 
 }
 
 // (MSYNTH_SMALLROWS=0: the row-tile matrix kernels take these layers, as before r05 -- the A/B of DESIGN section 8)
-bool small_rows_on() {
-    static const int on = [] { const char* e = getenv("MSYNTH_SMALLROWS"); return (e && atoi(e) == 0) ? 0 : 1; }();
-    return on != 0;
-}
+bool small_rows_on() { return ms_switch_on("MSYNTH_SMALLROWS"); }
 
 // 16 positions x (64 / S) output channels per workgroup, while that is at most two workgroups per CU
 bool ctl_plan(const ms_convt1d_desc* d, CtsP* q) {
@@ -233,13 +230,13 @@ bool mss_convt_applicable(const ms_convt1d_desc* d) {
     return ctl_plan(d, &q);
 }
 
-const char* mss_convt_name(const ms_convt1d_desc* d) { return d->stride == 8 ? "k_convt_lanes<8>" : "k_convt_lanes<2>"; }
+const char* mss_convt_name(int stride) { return stride == 8 ? "k_convt_lanes<8>" : "k_convt_lanes<2>"; }
 
 int mss_convt_fwd(const ms_convt1d_desc* d, const float* x, const float* w, const float* bias, float* y, hipStream_t s) {
     CtsP q;
     if (!ctl_plan(d, &q)) return MS_ERR_UNSUPPORTED;
     if (((uintptr_t)w) & 15) return MS_ERR_UNSUPPORTED;          // (16-byte weight loads: the caller falls through to the row-tile kernels)
-    ms_note_kernel(0, "%s", mss_convt_name(d));
+    ms_note_kernel(0, "%s", mss_convt_name(d->stride));
     const dim3 grid(ms_ceil_div(q.Lin, CL_JT), ms_ceil_div(q.Cout, 64 / d->stride), q.B);
     if (d->stride == 8) hipLaunchKernelGGL(k_convt_lanes<8>, grid, dim3(256), 0, s, q, x, w, bias, y);
     else hipLaunchKernelGGL(k_convt_lanes<2>, grid, dim3(256), 0, s, q, x, w, bias, y);

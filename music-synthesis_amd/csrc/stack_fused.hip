@@ -403,7 +403,7 @@ bool stack_ok(const ms_stack_desc* d) {
     if (d->C != 32 && d->C != 64) return false;
     if (d->L % 4) return false;
     if ((long long)d->B * d->C * d->L * 4 >= (1ll << 31)) return false;
-    static const bool np3 = getenv("MSYNTH_ATOM_NP") && atoi(getenv("MSYNTH_ATOM_NP")) == 3;     // (three-piece images: atom_fused.hip)
+    static const bool np3 = ms_switch_int("MSYNTH_ATOM_NP", 2) == 3;     // (three-piece images: atom_fused.hip; read once, ms_common.h)
     if (np3) return false;
     int halo = 0;
     for (int i = 0; i < d->count; ++i) {
@@ -418,8 +418,7 @@ bool stack_ok(const ms_stack_desc* d) {
 extern "C" {
 
 int ms_residual_stack_supported(const ms_stack_desc* d) {
-    const char* sw = getenv("MSYNTH_STACK");                     // tuning / test switch (0: one launch per atom)
-    if (sw && atoi(sw) == 0) return 0;
+    if (!ms_switch_on("MSYNTH_STACK")) return 0;                 // tuning / test switch (0: one launch per atom)
     return stack_ok(d) ? 1 : 0;
 }
 

@@ -211,8 +211,7 @@ int pick_nsplit8(const ConvP& p, int nsteps) {
 
 // p = mirrored conv of the transposed conv: Cin_T = p.Cout, Cout_T = p.Cin, Lin_T = p.Lout, Lout_T = p.Lin
 bool mswt8_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_WGRADT8");         // tuning / test switch (0: fp32-MFMA phase-split kernel)
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_WGRADT8")) return false;    // tuning / test switch (0: fp32-MFMA phase-split kernel)
     return p.stride == TS && p.K == TK && p.pad == TK / 4 && p.dil == 1 && p.groups == 1 && p.Lin == p.Lout * TS &&
            p.Lout % QS == 0 && p.Cout % TCI == 0 && p.Cin % TCO == 0 &&
            (long long)p.B * p.Cin * p.Lin * 4 < (1ll << 31) && (long long)p.B * p.Cout * p.Lout * 4 < (1ll << 31);

@@ -215,8 +215,7 @@ int pick_slices(const ConvP& p, int nsteps) {
 
 // p = mirrored conv of the transposed conv: Cin_T = p.Cout, Cout_T = p.Cin, Lin_T = p.Lout, Lout_T = p.Lin
 bool mswt2s_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_WGRADT2S");        // tuning / test switch (0: the generic weight-gradient kernels)
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_WGRADT2S")) return false;   // tuning / test switch (0: the generic weight-gradient kernels)
     const int W = p.Lout;
     return p.stride == 2 && p.K == 4 && p.pad == 1 && p.dil == 1 && p.groups == 1 && p.in_act == MS_ACT_NONE &&
            (p.act == MS_ACT_NONE || p.act == MS_ACT_LRELU) && p.Lin == 2 * W && (W == 4 || W == 8 || W == 16 || W == 32) &&

@@ -587,10 +587,7 @@ bool w5_geometry(const ConvP& p) {
            (long long)p.B * p.Cin * p.Lin * 4 < (1ll << 31);
 }
 
-bool w5_enabled() {
-    const char* e = getenv("MSYNTH_WGRAD5");          // tuning / test switch (0: fp32-MFMA row-tile kernel)
-    return !(e && atoi(e) == 0);
-}
+bool w5_enabled() { return ms_switch_on("MSYNTH_WGRAD5"); }     // tuning / test switch (0: fp32-MFMA row-tile kernel)
 
 // table of `n` parts (B[i], L[i]) of the layer c; pointers filled by the caller
 void w5_table(const ConvP& c, int n, const int* B, const int* L, W5P* q) {
@@ -631,8 +628,8 @@ int w5_launch(const ConvP& c, const W5P& q, bool vec, float* gw, float* gb, floa
 
 // ---- host side of the pre-split path
 bool w5_pre_enabled() {
-    const char* e = getenv("MSYNTH_W5_NP");            // tuning / test switch (3: the exact three-piece bf16 kernel, operands split
-    return !(e && atoi(e) == 3);                       //  in the loader)
+    static const bool pre = ms_switch_int("MSYNTH_W5_NP", 2) != 3;   // tuning / test switch (3: the exact three-piece bf16
+    return pre;                                                       //  kernel, operands split in the loader; read once, ms_common.h)
 }
 
 size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -724,7 +721,10 @@ size_t msw5_ws(const ConvP& p) {
     return n;
 }
 
-const char* msw5_name(const ConvP&) { return "k_wgrad_k5_split"; }
+const char* msw5_name(const ConvP& p) {     // (for 16-byte aligned operands and the workspace msw5_ws asks for)
+    const float* aligned = nullptr;
+    return w5_pre_ok(p, 1, &aligned, &aligned, &aligned) ? "k_wgrad_k5_pre" : "k_wgrad_k5_split";
+}
 
 int msw5_bwd_weight(const ConvP& p, const float* x, const float* gy, const float* y_act, float* gw, float* gb,
                     float beta, void* ws, size_t ws_bytes, hipStream_t s) {

@@ -910,8 +910,7 @@ void launch_wrows_ak(const WrPlan& q, const float* x, const float* gy, const flo
 
 // the split-bf16 kernel takes: the k3 atom convs (pad = dil in {1, 3, 9}), aligned rows of >= 64 samples, whole tiles
 bool wrows3_ok(const WrPlan& q, int K, int TM, bool vec, bool has_yact) {
-    const char* sw = getenv("MSYNTH_WROWS3");        // tuning / test switch (0: fp32-MFMA kernel)
-    if (sw && atoi(sw) == 0) return false;
+    if (!ms_switch_on("MSYNTH_WROWS3")) return false;    // tuning / test switch (0: fp32-MFMA kernel)
     const WrP& p = q.p;
     if (K != 3 || !vec || q.refl || !has_yact || p.g_kind != MS_ACT_LRELU || p.x_kind != MS_ACT_NONE) return false;
     if (p.R != 1 || p.Lt != KMAX || p.L % 64 || p.CK % CB || p.M % 64) return false;
@@ -946,7 +945,7 @@ void launch_wrows3_np(const WrPlan& q, const float* x, const float* gy, const fl
 }
 
 bool wrows3_scaled(const WrPlan& q) {
-    static const int sw = getenv("MSYNTH_WROWS3_NP") ? atoi(getenv("MSYNTH_WROWS3_NP")) : 2;      // tuning / test switch (3: bf16 x 3)
+    static const int sw = ms_switch_int("MSYNTH_WROWS3_NP", 2);      // tuning / test switch (3: bf16 x 3; read once, ms_common.h)
     if (sw == 3 || q.mp.n <= 0) return false;
     for (int i = 0; i < q.mp.n; ++i)
         if (!q.mp.xmax[i] || !q.mp.gmax[i]) return false;
@@ -1005,8 +1004,7 @@ void launch_wrows(const WrPlan& q, bool vec, const float* x, const float* gy, co
 }  // namespace
 
 bool msw_bwd_weight_applicable(const ConvP& p) {
-    const char* e = getenv("MSYNTH_WROWS");          // tuning / test switch (0 disables)
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_WROWS")) return false;     // tuning / test switch (0 disables)
     return plan_wrows(p).ok;
 }
 
@@ -1098,16 +1096,14 @@ void launch_wrows_t2(const WrPlan& q, const float* gy, const float* y_act, const
 }  // namespace
 
 size_t msw_convt_ws(const ConvP& c) {
-    const char* e = getenv("MSYNTH_WROWS");
-    if (e && atoi(e) == 0) return 0;
+    if (!ms_switch_on("MSYNTH_WROWS")) return 0;
     const WrPlan q = plan_wrows_t(c);
     return q.ok ? (size_t)q.nsplit * q.stride_floats * sizeof(float) : 0;
 }
 
 int msw_convt_dwq(const ConvP& c, const float* x, const float* gy, const float* y_act, float* dwq,
                   void* ws, size_t ws_bytes, hipStream_t s) {
-    const char* e = getenv("MSYNTH_WROWS");
-    if (e && atoi(e) == 0) return MS_ERR_UNSUPPORTED;
+    if (!ms_switch_on("MSYNTH_WROWS")) return MS_ERR_UNSUPPORTED;
     const WrPlan q = plan_wrows_t(c);
     if (!q.ok) return MS_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < (size_t)q.nsplit * q.stride_floats * sizeof(float)) return MS_ERR_UNSUPPORTED;
@@ -1236,8 +1232,7 @@ WrPlan plan_wrows_multi(const ConvP* cs, int n) {
 }  // namespace
 
 size_t msw_multi_ws(const ConvP* cs, int n) {
-    const char* e = getenv("MSYNTH_WMULTI");         // tuning / test switch (0 disables the batched launch)
-    if (e && atoi(e) == 0) return 0;
+    if (!ms_switch_on("MSYNTH_WMULTI")) return 0;        // tuning / test switch (0 disables the batched launch)
     const WrPlan q = plan_wrows_multi(cs, n);
     return q.ok ? (size_t)q.nsplit * q.stride_floats * sizeof(float) : 0;
 }
@@ -1245,7 +1240,7 @@ size_t msw_multi_ws(const ConvP* cs, int n) {
 // does the batched split kernel take these convs with SIGN WORDS in place of the activations (k_wgrad_rows3<., 2, true>)?
 bool msw_multi_takes_signs(const ConvP* cs, int n) {
     if (msw_multi_ws(cs, n) == 0) return false;
-    static const int sw = getenv("MSYNTH_WROWS3_NP") ? atoi(getenv("MSYNTH_WROWS3_NP")) : 2;
+    static const int sw = ms_switch_int("MSYNTH_WROWS3_NP", 2);
     if (sw == 3) return false;
     const WrPlan q = plan_wrows_multi(cs, n);
     return q.ok && wrows3_ok(q, 3, q.tm, true, true);
@@ -1469,8 +1464,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad32(W32P p, const float* __restr
 }  // namespace
 
 bool msw32_applicable(const ConvP& c) {
-    const char* e = getenv("MSYNTH_WROWS");
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_WROWS")) return false;
     return c.groups == 1 && c.stride == 1 && c.Lout == c.Lin && c.pad_mode == MS_PAD_ZERO && c.K == 3 &&
            c.Cout == 32 && c.Cin == 32 && c.dil >= 1 && c.dil <= 9 && c.pad == c.dil && !c.in_act &&
            c.Lin % 4 == 0 && c.Lin >= 64 && (c.act == MS_ACT_LRELU || c.act == MS_ACT_NONE) &&
@@ -1482,6 +1476,8 @@ static int w32_grid(const ConvP& c) {
     int g = ms_ceil_div(units, 4);
     return g > 512 ? 512 : g;
 }
+
+const char* msw32_name(const ConvP& c) { return c.act == MS_ACT_LRELU ? "k_wgrad32<1>" : "k_wgrad32<0>"; }
 
 size_t msw32_ws(const ConvP& c) { return (size_t)w32_grid(c) * (32 * 32 * 3 + 32) * sizeof(float); }
 
@@ -1513,8 +1509,7 @@ int msw32_bwd_weight(const ConvP& c, const float* x, const float* gy, const floa
 // n 32 -> 32 k3 LeakyReLU weight gradients of one length (a ResidualStack's six) in one launch pair:
 // each problem gets 512/n workgroups, i.e. n times more units per wave and the same slab bytes in total
 static bool w32_multi_ok(const ConvP* cs, int n) {
-    const char* e = getenv("MSYNTH_WMULTI");
-    if (e && atoi(e) == 0) return false;
+    if (!ms_switch_on("MSYNTH_WMULTI")) return false;
     if (n < 2 || n > WR_MULTI_MAX) return false;
     for (int i = 0; i < n; ++i) {
         if (!msw32_applicable(cs[i]) || cs[i].B != cs[0].B || cs[i].Lin != cs[0].Lin || cs[i].act != MS_ACT_LRELU ||

@@ -119,10 +119,7 @@ __global__ __launch_bounds__(256) void k_wgrad_short(WsP p, const float* __restr
     }
 }
 
-bool ws_enabled() {
-    const char* sw = getenv("MSYNTH_WSHORT");     // tuning / test switch (0: the im2col weight-gradient kernel)
-    return !(sw && atoi(sw) == 0);
-}
+bool ws_enabled() { return ms_switch_on("MSYNTH_WSHORT"); }    // tuning / test switch (0: the im2col weight-gradient kernel)
 
 bool ws_plan(const ConvP& c, WsP* p) {
     if (!ws_enabled() || c.pad_mode != MS_PAD_REFLECT) return false;
@@ -142,6 +139,8 @@ bool msws_applicable(const ConvP& c) {
     return ws_plan(c, &p);
 }
 
+const char* msws_name(const ConvP&) { return "k_wgrad_short"; }
+
 size_t msws_ws(const ConvP& c) {
     WsP p;
     return ws_plan(c, &p) ? (size_t)p.B * p.Cin * p.Lq * sizeof(float) : 0;
@@ -156,7 +155,7 @@ int msws_bwd_weight(const ConvP& c, const float* x, const float* gy, const float
     if (p.act != MS_ACT_NONE && !y_act) return MS_ERR_INVALID_ARG;
     float* xr = (float*)ws;
     const size_t n = (size_t)p.B * p.Cin * p.Lq;
-    ms_note_kernel(0, "k_wgrad_short");
+    ms_note_kernel(0, "%s", msws_name(c));
     hipLaunchKernelGGL(k_ws_pad_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, x, xr);
     MS_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_wgrad_short, dim3(p.Cout / 32, p.Cin / 4), dim3(256), 0, s, p, gy, y_act, xr, beta, gw, gb);

@@ -141,6 +141,67 @@ def test_discriminator_layers_are_one_launch_per_pass(lib):
     assert L.ms_conv1d_parts_launches(d, parts, 0, 0) < 0
 
 
+def _judge_parts(lib, B, x_offset=0, gx_offset=0):
+    """The discriminator's judge conv (1024 -> 1, k3) over the three scales; part 1's x / gx moved by the given bytes."""
+    d = lib.ConvDesc(B, 1024, 32, 1, 3, 1, 1, 1, 1, 0, 0, 0.2, 0)
+    parts = lib.ConvParts()
+    parts.count = 3
+    for i, Lin in enumerate((32, 17, 9)):
+        parts.B[i], parts.Lin[i] = B, Lin
+        for f, base in (("x", 0x10000000), ("y", 0x20000000), ("gy", 0x30000000), ("gx", 0x50000000)):
+            getattr(parts, f)[i] = base + 0x1000000 * i
+    parts.x[1] += x_offset
+    parts.gx[1] += gx_offset
+    return d, parts
+
+
+def test_parts_plan_sees_operand_alignment(lib):
+    """A part whose operand is not 16-byte aligned (a sliced view) sends the judge conv part by part: the launch count says so
+    and the workspace covers the per-part calls that then run (the query used to plan the one-launch kernel)."""
+    L = lib.load()
+    for B in (64, 32):
+        for which, offs in ((0, (4, 0)), (1, (0, 4)), (2, (4, 0))):
+            d, parts = _judge_parts(lib, B)
+            assert L.ms_conv1d_parts_launches(d, parts, which, 0) == 1
+            d, parts = _judge_parts(lib, B, *offs)
+            assert L.ms_conv1d_parts_launches(d, parts, which, 0) == 3, (B, which)
+            per_part = max(L.ms_conv1d_workspace_bytes(lib.ConvDesc(B, 1024, Lin, 1, 3, 1, 1, 1, 1, 0, 0, 0.2, 0), which)
+                           for Lin in (32, 17, 9))
+            assert L.ms_conv1d_parts_workspace_bytes(d, parts, which, 0) >= per_part, (B, which)
+
+
+def test_kernel_name_follows_the_dispatch(lib):
+    """ms_conv1d_kernel_name names the kernel the entry point runs for a call without residual / y_act."""
+    L = lib.load()
+
+    def name(args, which):
+        return L.ms_conv1d_kernel_name(lib.ConvDesc(*args), which).decode()
+
+    # a pre-activation (in_act) grouped conv: the grouped kernels take no input activation, the direct kernels run
+    grouped = (32, 16, 8192, 64, 41, 4, 20, 1, 4, 0, 1, 0.2, 1)
+    assert name(grouped, 0).startswith("k_conv1d_fwd_direct<"), name(grouped, 0)
+    assert name(grouped, 2).startswith("k_conv1d_bwd_weight_direct<"), name(grouped, 2)
+    # reflection padding: the backward data runs on the zero-padded geometry, rows padded to a multiple of 4 included
+    k5 = (64, 1024, 17, 1024, 5, 1, 2, 1, 1, 0, 1, 0.2, 0)
+    assert name(k5[:9] + (1,) + k5[10:], 1) == name(k5, 1)
+    # ... and a strided or grouped reflection-padded conv has no backward data at all
+    assert name((32, 16, 8192, 64, 41, 4, 20, 1, 4, 1, 1, 0.2, 0), 1) == ""
+
+
+def test_environment_is_read_only_through_the_switch_helpers():
+    csrc = os.path.join(ROOT, "music-synthesis_amd", "csrc")
+    hits = {}
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h", ".cpp", ".cc")):
+            n = open(os.path.join(csrc, fn)).read().count("getenv")
+            if n:
+                hits[fn] = n
+    assert hits == {"ms_common.h": 1}, hits
+    text = open(os.path.join(csrc, "ms_common.h")).read()
+    body = text[text.index("static inline int ms_switch_int("):]
+    assert body.index("getenv") < body.index("}")
+
+
 def test_struct_layout(lib):
     assert ctypes.sizeof(lib.ConvDesc) == 13 * 4
     assert ctypes.sizeof(lib.ConvTDesc) == 10 * 4
