@@ -551,6 +551,18 @@ int ms_audio2mel_frames(int32_t N, int32_t n_fft, int32_t hop);
 int ms_audio2mel_fwd(const float* audio, int32_t B, int32_t N, const float* window, int32_t n_fft,
                      int32_t hop, const float* mel_basis, int32_t n_mel, float* out,
                      ms_stream_t stream);
+/*
+ * Autograd of Audio2Mel.forward w.r.t. the audio: grad_audio (B, N) = d loss / d audio for grad_out (B, n_mel, frames)
+ * = d loss / d out.  The spectrum is recomputed from `audio` (bitwise the forward's, so the clamp mask agrees); the
+ * clamp passes the gradient where mel >= 1e-5, and a bin with |X| = 0 contributes 0 (torch.abs of a complex tensor).
+ * Deterministic: no atomics.  workspace >= ms_audio2mel_bwd_workspace_bytes(B, N, n_fft, hop) (0: invalid geometry).
+ * Same argument checks and status codes as ms_audio2mel_fwd, plus MS_ERR_WORKSPACE, and MS_ERR_UNSUPPORTED when
+ * (2 n_fft + n_fft/2 + 1 + n_mel) floats exceed 64 KiB of LDS.
+ */
+size_t ms_audio2mel_bwd_workspace_bytes(int32_t B, int32_t N, int32_t n_fft, int32_t hop);
+int ms_audio2mel_bwd(const float* audio, int32_t B, int32_t N, const float* window, int32_t n_fft, int32_t hop,
+                     const float* mel_basis, int32_t n_mel, const float* grad_out, float* grad_audio,
+                     void* workspace, size_t workspace_bytes, ms_stream_t stream);
 
 /*
  * audio() front-end of the dataset pass (feature/feature.py:64-71): librosa.resample (default 'kaiser_best':

@@ -311,6 +311,25 @@ class L1MeanFn(Function):
         return gr, gf
 
 
+class Audio2MelFn(Function):
+    """Audio2Mel.forward (feature/feature.py:39-59) on (B, N) audio, differentiable w.r.t. the audio.  Saves the
+    audio only: the backward kernel recomputes the spectrum."""
+
+    @staticmethod
+    def forward(ctx, audio, window, basis, n_fft, hop):
+        ctx.save_for_backward(audio, window, basis)
+        ctx.geom = (n_fft, hop)
+        return P.audio2mel(audio, window, basis, n_fft, hop)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise NotImplementedError("Audio2Mel: gradients w.r.t. window / mel_basis are not implemented")
+        audio, window, basis = ctx.saved_tensors
+        ga = P.audio2mel_bwd(audio, window, basis, *ctx.geom, _c(g)) if ctx.needs_input_grad[0] else None
+        return ga, None, None, None, None
+
+
 class LsGFn(Function):
     @staticmethod
     def forward(ctx, j):

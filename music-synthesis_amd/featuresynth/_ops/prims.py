@@ -1000,6 +1000,25 @@ def audio2mel(audio, window, basis, n_fft, hop):
     return out
 
 
+def audio2mel_bwd(audio, window, basis, n_fft, hop, grad_out):
+    """d loss / d audio (B, N) of audio2mel for grad_out = d loss / d out (B, n_mel, frames); the spectrum is
+    recomputed from the audio, the scratch comes from torch's allocator (capture-safe)."""
+    L.require(audio, "audio"); L.require(window, "window"); L.require(basis, "mel_basis")
+    L.require(grad_out, "Audio2Mel output gradient")
+    B, N = audio.shape
+    n_mel = basis.shape[0]
+    lib = L.load()
+    shape = (B, n_mel, lib.ms_audio2mel_frames(N, n_fft, hop))
+    if tuple(grad_out.shape) != shape:
+        raise RuntimeError("Audio2Mel backward: output gradient %s != %s" % (tuple(grad_out.shape), shape))
+    grad = torch.empty_like(audio)
+    nws = lib.ms_audio2mel_bwd_workspace_bytes(B, N, n_fft, hop)
+    ws = L.workspace(nws, audio.device)
+    L.call("ms_audio2mel_bwd", None, audio.data_ptr(), B, N, window.data_ptr(), n_fft, hop, basis.data_ptr(), n_mel,
+           grad_out.data_ptr(), grad.data_ptr(), L.ptr(ws), nws, L.stream())
+    return grad
+
+
 def resample_sinc(x, ratio, interp_win, interp_delta, num_table):
     """x (rows, n_in) -> (rows, ceil(n_in * ratio)): band-limited sinc interpolation with the given half window."""
     L.require(x, "audio"); L.require(interp_win, "interp_win"); L.require(interp_delta, "interp_delta")

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .._ops import functional as F_
 from .._ops import prims as P
 
 
@@ -88,6 +89,8 @@ class Audio2Mel(nn.Module):
         if audio.dim() != 3 or audio.shape[1] != 1:
             raise RuntimeError("Audio2Mel expects (B, 1, N) audio, got %s" % (tuple(audio.shape),))
         a = audio.reshape(audio.shape[0], audio.shape[2]).contiguous().float()
+        if a.requires_grad:     # a mel loss on generated audio: the HIP backward (csrc/audio2mel.hip)
+            return F_.Audio2MelFn.apply(a, self.window, self.mel_basis, self.n_fft, self.hop_length)
         return P.audio2mel(a, self.window, self.mel_basis, self.n_fft, self.hop_length)
 
 

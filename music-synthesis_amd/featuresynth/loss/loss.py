@@ -1,9 +1,12 @@
 """GAN losses of the hot path with the call signatures of the reference's
 featuresynth/loss/loss.py (hinge :9-18, least squares :5-14, mel_gan_disc_loss :21-25,
-mel_gan_feature_loss :28-65, mel_gan_gen_loss :68-78).  Each returns a 0-d tensor with autograd;
+mel_gan_feature_loss :28-65, mel_gan_gen_loss :68-78), plus the mel-spectrogram L1 term of later MelGAN-family
+training (MelReconstructionLoss; no counterpart in the reference).  Each returns a 0-d tensor with autograd;
 the reductions are wavefront-shuffle HIP kernels and the composite losses are single autograd
 nodes (one fused backward over the 18 feature maps).
 """
+import torch
+
 from .._ops import functional as F_
 
 
@@ -75,3 +78,22 @@ def mel_gan_gen_loss(real_features, fake_features, real_judgements, fake_judgeme
         term = gan_loss(f)
         j_loss = term if j_loss is None else j_loss + term
     return j_loss + feature_loss_weight * mel_gan_feature_loss(real_features, fake_features)
+
+
+class MelReconstructionLoss(object):
+    """weight * mean(|A2M(fake) - A2M(samples)|) for an Audio2Mel module A2M (feature/feature.py): the mel-spectrogram
+    L1 term a GAN vocoder's generator step adds to its adversarial loss (GeneratorTrainer.spectral_loss).  The real
+    side carries no gradient; the fake side backpropagates through the HIP Audio2Mel backward (csrc/audio2mel.hip)."""
+
+    def __init__(self, audio2mel, weight=45.0):
+        self.audio2mel = audio2mel
+        self.weight = float(weight)
+
+    def target(self, samples):
+        """A2M(samples), computed under no_grad (the trainer runs it beside D(samples) on the real-path stream)."""
+        with torch.no_grad():
+            return self.audio2mel(samples)
+
+    def __call__(self, fake, samples, target=None):
+        real = self.target(samples) if target is None else target
+        return self.weight * F_.L1MeanFn.apply(real, self.audio2mel(fake))

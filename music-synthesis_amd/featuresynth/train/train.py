@@ -28,7 +28,7 @@ from .. import _dist
 from .._ops import graph as _graph
 from .._ops import functional as _F
 from .._ops import step as _step
-from ..loss import hinge_discriminator_loss, hinge_generator_loss
+from ..loss import MelReconstructionLoss, hinge_discriminator_loss, hinge_generator_loss
 from ..loss import mel_gan_disc_loss as _mel_gan_disc_loss
 from ..loss import mel_gan_gen_loss as _mel_gan_gen_loss
 from ..optim import FlatAdam
@@ -383,9 +383,26 @@ class GeneratorTrainer(_TrainerBase):
     def __init__(self, generator, g_optim, discriminator, d_optim, loss,
                  sub_loss=hinge_generator_loss):
         super().__init__(generator, g_optim, discriminator, d_optim, loss, sub_loss)
+        self.spectral_loss = None
+
+    @property
+    def spectral_loss(self):
+        """None, or an extra term `spectral_loss(fake, samples)` -> 0-d tensor that the step adds to the GAN loss before
+        backward(), e.g. loss.MelReconstructionLoss (not in the reference); `g_loss` then reports the sum.  An attribute,
+        not a constructor argument: the constructor keeps the reference's signature (train.py:9-16)."""
+        return self._spectral_loss
+
+    @spectral_loss.setter
+    def spectral_loss(self, fn):
+        self._spectral_loss = fn
+        self._runner = None         # a step captured without (or with another) term is re-planned
 
     def _stepped_optim(self):
         return self.g_optim
+
+    def _direct_ok(self):
+        # the hand-scheduled step knows only the GAN loss: a spectral term takes the generic native path
+        return self.spectral_loss is None and super()._direct_ok()
 
     def _stock_losses(self):
         return self.loss is _mel_gan_gen_loss and self.sub_loss is hinge_generator_loss
@@ -412,12 +429,19 @@ class GeneratorTrainer(_TrainerBase):
             main = torch.cuda.current_stream(samples.device)
             side = _graph.aux_stream(samples.device)
             side.wait_stream(main)
+            real_mel = None
             with _graph.forked(side), torch.no_grad():
                 r_features, r_score = self.discriminator(samples, features)
+                if isinstance(self.spectral_loss, MelReconstructionLoss):
+                    real_mel = self.spectral_loss.target(samples)
             fake = self.generator(features)
             f_features, f_score = self.discriminator(fake, features)
             main.wait_stream(side)
             loss = self.loss(r_features, f_features, r_score, f_score, gan_loss=self.sub_loss)
+            if real_mel is not None:
+                loss = loss + self.spectral_loss(fake, samples, target=real_mel)
+            elif self.spectral_loss is not None:
+                loss = loss + self.spectral_loss(fake, samples)
             loss.backward()
             _graph.join_side_streams(samples.device)      # (modules that fork streams inside their forward: realmelgan)
         finally:
@@ -437,6 +461,8 @@ class GeneratorTrainer(_TrainerBase):
         f_features, f_score = self.discriminator(fake, features)
         r_features, r_score = self.discriminator(samples, features)
         loss = self.loss(r_features, f_features, r_score, f_score, gan_loss=self.sub_loss)
+        if self.spectral_loss is not None:
+            loss = loss + self.spectral_loss(fake, samples)
         loss.backward()
         self.g_optim.step()
         if isinstance(fake, dict):
