@@ -565,6 +565,49 @@ int ms_audio2mel_bwd(const float* audio, int32_t B, int32_t N, const float* wind
                      void* workspace, size_t workspace_bytes, ms_stream_t stream);
 
 /*
+ * STFTMagnitude: mag = sqrt(clamp(|X|^2, min_power)) for X = torch.stft(audio, n_fft, hop, window, center=True,
+ * pad_mode='reflect') -- n_fft/2 reflect-padded samples on either side, frame f starts at padded position f*hop.
+ * audio (B, N); window (n_fft): the analysis window already zero-padded (centred) to n_fft; mag is stored FRAME-MAJOR,
+ * (B, frames, n_fft/2+1), frames = ms_stft_frames(N, n_fft, hop) = 1 + N/hop (0: invalid geometry).
+ * n_fft must be a power of two in [64, 4096] (else MS_ERR_UNSUPPORTED), hop >= 1, N > n_fft/2 (the reflect pad must fit:
+ * else MS_ERR_INVALID_ARG), min_power >= 0, B <= 65535.
+ */
+int ms_stft_frames(int32_t N, int32_t n_fft, int32_t hop);
+int ms_stft_mag_fwd(const float* audio, int32_t B, int32_t N, const float* window, int32_t n_fft, int32_t hop,
+                    float min_power, float* mag, ms_stream_t stream);
+/*
+ * Autograd of ms_stft_mag_fwd w.r.t. the audio: grad_audio (B, N) for grad_mag (B, frames, n_fft/2+1) = d loss / d mag.
+ * The spectrum is recomputed from `audio` (bitwise the forward's, so the clamp mask agrees): a bin whose power is below
+ * min_power passes no gradient, and a bin with |X| = 0 contributes 0.  The frames over a sample -- and over the reflect-pad
+ * positions that mirror onto it -- are summed in a fixed order without atomics: deterministic.
+ * workspace >= ms_stft_mag_bwd_workspace_bytes(B, N, n_fft, hop) = B * frames * n_fft floats (0: invalid geometry).
+ * Same argument checks and status codes as ms_stft_mag_fwd, plus MS_ERR_WORKSPACE.
+ */
+size_t ms_stft_mag_bwd_workspace_bytes(int32_t B, int32_t N, int32_t n_fft, int32_t hop);
+int ms_stft_mag_bwd(const float* audio, int32_t B, int32_t N, const float* window, int32_t n_fft, int32_t hop,
+                    float min_power, const float* grad_mag, float* grad_audio, void* workspace,
+                    size_t workspace_bytes, ms_stream_t stream);
+/*
+ * One resolution of a multi-resolution STFT loss on fake magnitudes f and real magnitudes r (n elements each, same
+ * layout, all > 0):
+ *     sc = ||r - f||_2 / ||r||_2        lm = (1/n) sum |log r - log f|        out[0] = sc_weight * sc + mag_weight * lm
+ *   _target  r_sumsq[0] = sum r^2 (computed once with the target)
+ *   _fwd     sums[0..3) = {sum (r-f)^2, sum r^2, sum |log r - log f|} and out[0]; sc := 0 where a norm is 0
+ *   _bwd     grad_f = gout[0] * (sc_weight * (f - r) / (||r|| ||r - f||) + mag_weight * sign(f - r) / (n f)), the norms
+ *            read from `sums` in DEVICE memory (no host round trip: capturable); the first term := 0 where ||r - f|| = 0
+ * Per-workgroup partial sums by wave shuffles, then a fixed-order finish: no atomics, deterministic.
+ * workspace >= ms_stft_pair_loss_workspace_bytes(n) for _target and _fwd (MS_ERR_WORKSPACE otherwise).
+ */
+size_t ms_stft_pair_loss_workspace_bytes(int64_t n);
+int ms_stft_pair_loss_target(const float* r, int64_t n, float* r_sumsq, void* workspace, size_t workspace_bytes,
+                             ms_stream_t stream);
+int ms_stft_pair_loss_fwd(const float* f, const float* r, int64_t n, const float* r_sumsq, float sc_weight,
+                          float mag_weight, float* sums, float* out, void* workspace, size_t workspace_bytes,
+                          ms_stream_t stream);
+int ms_stft_pair_loss_bwd(const float* f, const float* r, int64_t n, const float* sums, const float* gout,
+                          float sc_weight, float mag_weight, float* grad_f, ms_stream_t stream);
+
+/*
  * audio() front-end of the dataset pass (feature/feature.py:64-71): librosa.resample (default 'kaiser_best':
  * resampy's interpolated Kaiser-windowed sinc) and librosa.util.normalize(x) * 0.95.
  * x (rows, n_in) -> y (rows, n_out) with n_out = ceil(n_in * ratio), ratio = target_sr / orig_sr.

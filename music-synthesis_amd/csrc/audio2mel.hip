@@ -8,40 +8,18 @@
 // through log10 and the clamp, projects it back through the filters' nonzero supports, scales by X/|X| and
 // runs the inverse FFT in LDS; the windowed frame gradients land in a per-frame workspace and a gather
 // kernel sums the <= n_fft/hop frames over each sample in frame order (no atomics: bitwise reproducible).
-#include "ms_common.h"
+#include "frame_fft.h"
 
 namespace {
 
 // The windowed, right-zero-padded frame at sample `start` of row `a` -> X[0 .. n_fft) in natural order in
-// re / im.  Forward and backward run this one body, and the butterfly spells out the fused multiply-adds the
-// forward compiles to, so the backward's recomputed spectrum -- and with it the clamp mask -- is bitwise the
-// forward's.
+// re / im: the shared in-LDS FFT (frame_fft.h) fed by this kernel family's frame load.
 __device__ __forceinline__ void a2m_frame_fft(const float* __restrict__ a, int N, const float* __restrict__ window,
                                               int n_fft, int log2n, int start, float* re, float* im) {
-    for (int i = threadIdx.x; i < n_fft; i += 256) {
+    ms_frame_fft<float>([=](int i) {
         const int s = start + i;
-        const float v = (s < N ? a[s] : 0.f) * window[i];  // right zero-padding, feature.py:44-45
-        const int r = (int)(__brev((unsigned)i) >> (32 - log2n));
-        re[r] = v;
-        im[r] = 0.f;
-    }
-    __syncthreads();
-    for (int st = 1; st <= log2n; ++st) {
-        const int m = 1 << st, half = m >> 1;
-        for (int j = threadIdx.x; j < (n_fft >> 1); j += 256) {
-            const int grp = j / half, pos = j - grp * half;
-            const int i0 = grp * m + pos, i1 = i0 + half;
-            float sn, cs;
-            sincospif(2.0f * (float)pos / (float)m, &sn, &cs);  // w = exp(-2 pi i pos / m)
-            const float xr = re[i1], xi = im[i1];
-            const float tr = fmaf(xr, cs, xi * sn);
-            const float ti = fmaf(xi, cs, -(xr * sn));
-            const float ur = re[i0], ui = im[i0];
-            re[i0] = ur + tr; im[i0] = ui + ti;
-            re[i1] = ur - tr; im[i1] = ui - ti;
-        }
-        __syncthreads();
-    }
+        return s < N ? a[s] : 0.f;  // right zero-padding, feature.py:44-45
+    }, window, n_fft, log2n, re, im);
 }
 
 __device__ __forceinline__ float a2m_mag(float r, float q) {
@@ -173,22 +151,9 @@ __global__ __launch_bounds__(256) void k_audio2mel_bwd_frame(const float* __rest
         im[k] = k < nb ? im[k] * sc : 0.f;
     }
     __syncthreads();
-    // d/d u[n] = Re sum_k G[k] exp(+2 pi i k n / n_fft): radix-2 decimation in frequency, natural order in,
-    // bit-reversed order out (so the gradient spectrum is written in place above, with no permutation)
-    for (int half = n_fft >> 1; half >= 1; half >>= 1) {
-        const int m = half << 1;
-        for (int j = threadIdx.x; j < (n_fft >> 1); j += 256) {
-            const int grp = j / half, pos = j - grp * half;
-            const int i0 = grp * m + pos, i1 = i0 + half;
-            float sn, cs;
-            sincospif(2.0f * (float)pos / (float)m, &sn, &cs);  // w = exp(+2 pi i pos / m)
-            const float ar = re[i0], ai = im[i0], cr = re[i1], ci = im[i1];
-            const float dr = ar - cr, di = ai - ci;
-            re[i0] = ar + cr; im[i0] = ai + ci;
-            re[i1] = dr * cs - di * sn; im[i1] = dr * sn + di * cs;
-        }
-        __syncthreads();
-    }
+    // d/d u[n] = Re sum_k G[k] exp(+2 pi i k n / n_fft), bit-reversed order out (so the gradient spectrum is written
+    // in place above, with no permutation)
+    ms_frame_ifft_bitrev(n_fft, re, im);
     float* gf = gframes + ((size_t)b * frames + fr) * n_fft;
     for (int n = threadIdx.x; n < n_fft; n += 256)
         gf[n] = window[n] * re[(int)(__brev((unsigned)n) >> (32 - log2n))];
@@ -208,11 +173,7 @@ __global__ __launch_bounds__(256) void k_audio2mel_bwd_gather(const float* __res
     grad_audio[(size_t)b * N + s] = acc;
 }
 
-int a2m_log2(int n_fft) {    // log2(n_fft), or -1 when n_fft is not a power of two in [64, 4096]
-    int log2n = 0;
-    while ((1 << log2n) < n_fft && log2n < 13) ++log2n;
-    return ((1 << log2n) != n_fft || n_fft < 64 || n_fft > 4096) ? -1 : log2n;
-}
+int a2m_log2(int n_fft) { return ms_frame_log2(n_fft); }
 
 const size_t A2M_BWD_LDS_MAX = 64 * 1024;
 

@@ -330,6 +330,47 @@ class Audio2MelFn(Function):
         return ga, None, None, None, None
 
 
+class STFTMagFn(Function):
+    """feature.STFTMagnitude on (B, N) audio, differentiable w.r.t. the audio.  Saves the audio only: the backward
+    kernel recomputes the spectrum (csrc/stft_mag.hip)."""
+
+    @staticmethod
+    def forward(ctx, audio, window, n_fft, hop, min_power):
+        ctx.save_for_backward(audio, window)
+        ctx.geom = (n_fft, hop, min_power)
+        return P.stft_mag(audio, window, n_fft, hop, min_power)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("STFTMagnitude: the gradient w.r.t. the window is not implemented")
+        audio, window = ctx.saved_tensors
+        ga = P.stft_mag_bwd(audio, window, *ctx.geom, g) if ctx.needs_input_grad[0] else None
+        return ga, None, None, None, None
+
+
+class STFTPairLossFn(Function):
+    """sc_weight * ||real - fake||_2 / ||real||_2 + mag_weight * mean|log real - log fake| on two (B, bins, frames)
+    magnitude tensors; `r_sumsq` is the target's sum(real^2).  The gradient reaches the fake side only and reads the
+    norms from device memory."""
+
+    @staticmethod
+    def forward(ctx, fake, real, r_sumsq, sc_weight, mag_weight):
+        f, r = P.frame_major(fake, "fake magnitudes"), P.frame_major(real, "real magnitudes")
+        out, sums = P.stft_pair_loss_fwd(f, r, r_sumsq, sc_weight, mag_weight)
+        ctx.save_for_backward(f, r, sums)
+        ctx.weights = (sc_weight, mag_weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise NotImplementedError("stft pair loss: the real side carries no gradient")
+        f, r, sums = ctx.saved_tensors
+        gf = P.stft_pair_loss_bwd(f, r, sums, _c(g), *ctx.weights).transpose(1, 2) if ctx.needs_input_grad[0] else None
+        return gf, None, None, None, None
+
+
 class LsGFn(Function):
     @staticmethod
     def forward(ctx, j):

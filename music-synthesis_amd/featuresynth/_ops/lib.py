@@ -217,6 +217,14 @@ SIGNATURES = {
     "ms_audio2mel_fwd": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
     "ms_audio2mel_bwd_workspace_bytes": (_sz, [_c_int, _c_int, _c_int, _c_int]),
     "ms_audio2mel_bwd": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _sz, _vp]),
+    "ms_stft_frames": (_c_int, [_c_int, _c_int, _c_int]),
+    "ms_stft_mag_fwd": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_f, _vp, _vp]),
+    "ms_stft_mag_bwd_workspace_bytes": (_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "ms_stft_mag_bwd": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_f, _vp, _vp, _vp, _sz, _vp]),
+    "ms_stft_pair_loss_workspace_bytes": (_sz, [_c_i64]),
+    "ms_stft_pair_loss_target": (_c_int, [_vp, _c_i64, _vp, _vp, _sz, _vp]),
+    "ms_stft_pair_loss_fwd": (_c_int, [_vp, _vp, _c_i64, _vp, _c_f, _c_f, _vp, _vp, _vp, _sz, _vp]),
+    "ms_stft_pair_loss_bwd": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_f, _c_f, _vp, _vp]),
     "ms_resample_sinc_fwd": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, ctypes.c_double, _vp, _vp, _c_int, _c_int, _vp]),
     "ms_peak_normalize": (_c_int, [_vp, _c_int, _c_int, _c_f, _vp, _vp]),
     "ms_comm_unique_id": (_c_int, [_vp]),

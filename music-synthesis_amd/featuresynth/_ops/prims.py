@@ -1019,6 +1019,84 @@ def audio2mel_bwd(audio, window, basis, n_fft, hop, grad_out):
     return grad
 
 
+def stft_mag(audio, window, n_fft, hop, min_power):
+    """sqrt(clamp(|STFT|^2, min_power)) of (B, N) audio, torch.stft's center=True / reflect framing; `window` is the
+    n_fft-long (zero-padded) analysis window.  -> (B, n_fft/2+1, frames), a transposed view of the frame-major
+    storage the kernel writes."""
+    L.require(audio, "audio"); L.require(window, "window")
+    B, N = audio.shape
+    if window.numel() != n_fft:
+        raise RuntimeError("STFTMagnitude: the window holds %d values, n_fft is %d" % (window.numel(), n_fft))
+    lib = L.load()
+    frames = lib.ms_stft_frames(N, n_fft, hop)
+    if frames <= 0:
+        raise RuntimeError("STFTMagnitude: %d samples are too few for the %d-sample reflect pad" % (N, n_fft // 2))
+    mag = torch.empty((B, frames, n_fft // 2 + 1), dtype=torch.float32, device=audio.device)
+    L.call("ms_stft_mag_fwd", None, audio.data_ptr(), B, N, window.data_ptr(), n_fft, hop, float(min_power),
+           mag.data_ptr(), L.stream())
+    return mag.transpose(1, 2)
+
+
+def frame_major(t, name):
+    """The contiguous (B, frames, bins) tensor under a (B, bins, frames) magnitude-shaped tensor: the storage itself
+    when `t` is the transposed view stft_mag returns, a copy otherwise."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise RuntimeError("%s: expected a (B, bins, frames) tensor" % name)
+    return L.require(t.transpose(1, 2).contiguous(), name)
+
+
+def stft_mag_bwd(audio, window, n_fft, hop, min_power, grad_mag):
+    """d loss / d audio (B, N) of stft_mag for grad_mag = d loss / d mag (B, n_fft/2+1, frames); the spectrum is
+    recomputed from the audio, the scratch comes from torch's allocator (capture-safe)."""
+    L.require(audio, "audio"); L.require(window, "window")
+    B, N = audio.shape
+    lib = L.load()
+    shape = (B, n_fft // 2 + 1, lib.ms_stft_frames(N, n_fft, hop))
+    if tuple(grad_mag.shape) != shape:
+        raise RuntimeError("STFTMagnitude backward: output gradient %s != %s" % (tuple(grad_mag.shape), shape))
+    g = frame_major(grad_mag, "STFTMagnitude output gradient")
+    grad = torch.empty_like(audio)
+    nws = lib.ms_stft_mag_bwd_workspace_bytes(B, N, n_fft, hop)
+    ws = L.workspace(nws, audio.device)
+    L.call("ms_stft_mag_bwd", None, audio.data_ptr(), B, N, window.data_ptr(), n_fft, hop, float(min_power),
+           g.data_ptr(), grad.data_ptr(), L.ptr(ws), nws, L.stream())
+    return grad
+
+
+def stft_pair_target(real):
+    """-> 1-element tensor sum(real^2) for frame-major real magnitudes."""
+    L.require(real, "real magnitudes")
+    out = torch.empty((1,), dtype=torch.float32, device=real.device)
+    nws = L.load().ms_stft_pair_loss_workspace_bytes(real.numel())
+    ws = L.workspace(nws, real.device)
+    L.call("ms_stft_pair_loss_target", None, real.data_ptr(), real.numel(), out.data_ptr(), L.ptr(ws), nws, L.stream())
+    return out
+
+
+def stft_pair_loss_fwd(fake, real, r_sumsq, sc_weight, mag_weight):
+    """-> (0-d loss sc_weight * ||r-f|| / ||r|| + mag_weight * mean|log r - log f|, the three sums the backward reads)
+    for frame-major magnitudes of one layout."""
+    L.require(fake, "fake magnitudes"); L.require(real, "real magnitudes"); L.require(r_sumsq, "sum of real^2")
+    if fake.shape != real.shape:
+        raise RuntimeError("stft pair loss: shape mismatch %s vs %s" % (tuple(fake.shape), tuple(real.shape)))
+    out = torch.empty((), dtype=torch.float32, device=fake.device)
+    sums = torch.empty((3,), dtype=torch.float32, device=fake.device)
+    nws = L.load().ms_stft_pair_loss_workspace_bytes(fake.numel())
+    ws = L.workspace(nws, fake.device)
+    L.call("ms_stft_pair_loss_fwd", None, fake.data_ptr(), real.data_ptr(), fake.numel(), r_sumsq.data_ptr(),
+           float(sc_weight), float(mag_weight), sums.data_ptr(), out.data_ptr(), L.ptr(ws), nws, L.stream())
+    return out, sums
+
+
+def stft_pair_loss_bwd(fake, real, sums, gout, sc_weight, mag_weight):
+    """d loss / d fake (frame-major, as fake) for the 0-d upstream gradient gout, the norms read on the device."""
+    L.require(gout, "loss gradient")
+    grad = torch.empty_like(fake)
+    L.call("ms_stft_pair_loss_bwd", None, fake.data_ptr(), real.data_ptr(), fake.numel(), sums.data_ptr(),
+           gout.data_ptr(), float(sc_weight), float(mag_weight), grad.data_ptr(), L.stream())
+    return grad
+
+
 def resample_sinc(x, ratio, interp_win, interp_delta, num_table):
     """x (rows, n_in) -> (rows, ceil(n_in * ratio)): band-limited sinc interpolation with the given half window."""
     L.require(x, "audio"); L.require(interp_win, "interp_win"); L.require(interp_delta, "interp_delta")

@@ -1,1 +1,1 @@
-from .feature import Audio2Mel, audio_from_samples, resample  # noqa: F401
+from .feature import Audio2Mel, STFTMagnitude, audio_from_samples, resample  # noqa: F401

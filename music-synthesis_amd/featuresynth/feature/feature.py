@@ -94,6 +94,49 @@ class Audio2Mel(nn.Module):
         return P.audio2mel(a, self.window, self.mel_basis, self.n_fft, self.hop_length)
 
 
+class STFTMagnitude(nn.Module):
+    """Linear-magnitude STFT with torch.stft's default framing (not in the reference: what a multi-resolution STFT loss
+    is built from):
+
+        X   = torch.stft(audio[:, 0], n_fft, hop_length, win_length, hann_window(win_length), center=True,
+                         pad_mode='reflect', return_complex=True)
+        mag = sqrt(clamp(X.real**2 + X.imag**2, min=min_power))          (B, n_fft/2+1, 1 + N//hop_length)
+
+    Buffer `window`: the periodic hann window of win_length samples, zero-padded on both sides (centred) to n_fft.
+    n_fft is a power of two in [64, 4096], 1 <= win_length <= n_fft, any hop_length >= 1, N > n_fft/2.  Differentiable
+    w.r.t. audio that requires grad (csrc/stft_mag.hip; bins below min_power pass no gradient); the returned tensor
+    is a transposed view of frame-major storage."""
+
+    def __init__(self, n_fft, hop_length, win_length, min_power=1e-7):
+        super().__init__()
+        n_fft, hop_length, win_length = int(n_fft), int(hop_length), int(win_length)
+        if n_fft < 64 or n_fft > 4096 or n_fft & (n_fft - 1):
+            raise ValueError("STFTMagnitude: n_fft must be a power of two in [64, 4096], got %d" % n_fft)
+        if not 1 <= win_length <= n_fft:
+            raise ValueError("STFTMagnitude: win_length must be in [1, n_fft], got %d" % win_length)
+        if hop_length < 1:
+            raise ValueError("STFTMagnitude: hop_length must be >= 1, got %d" % hop_length)
+        if not min_power >= 0:
+            raise ValueError("STFTMagnitude: min_power must be >= 0, got %r" % (min_power,))
+        n = torch.arange(win_length, dtype=torch.float64)
+        window = torch.zeros(n_fft, dtype=torch.float32)
+        left = (n_fft - win_length) // 2
+        window[left:left + win_length] = (0.5 - 0.5 * torch.cos(2.0 * np.pi * n / win_length)).float()  # periodic hann
+        self.register_buffer("window", window)
+        self.n_fft = n_fft
+        self.hop_length = hop_length
+        self.win_length = win_length
+        self.min_power = float(min_power)
+
+    def forward(self, audio):
+        if audio.dim() != 3 or audio.shape[1] != 1:
+            raise RuntimeError("STFTMagnitude expects (B, 1, N) audio, got %s" % (tuple(audio.shape),))
+        a = audio.reshape(audio.shape[0], audio.shape[2]).contiguous().float()
+        if a.requires_grad:
+            return F_.STFTMagFn.apply(a, self.window, self.n_fft, self.hop_length, self.min_power)
+        return P.stft_mag(a, self.window, self.n_fft, self.hop_length, self.min_power)
+
+
 # resampy 'kaiser_best' (librosa.resample's default res_type in librosa < 0.10): published filter parameters
 KAISER_BEST = dict(num_zeros=64, precision=9, rolloff=0.9475937167399596, beta=14.769656459379492)
 

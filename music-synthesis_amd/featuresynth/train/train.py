@@ -28,7 +28,7 @@ from .. import _dist
 from .._ops import graph as _graph
 from .._ops import functional as _F
 from .._ops import step as _step
-from ..loss import MelReconstructionLoss, hinge_discriminator_loss, hinge_generator_loss
+from ..loss import hinge_discriminator_loss, hinge_generator_loss
 from ..loss import mel_gan_disc_loss as _mel_gan_disc_loss
 from ..loss import mel_gan_gen_loss as _mel_gan_gen_loss
 from ..optim import FlatAdam
@@ -388,8 +388,10 @@ class GeneratorTrainer(_TrainerBase):
     @property
     def spectral_loss(self):
         """None, or an extra term `spectral_loss(fake, samples)` -> 0-d tensor that the step adds to the GAN loss before
-        backward(), e.g. loss.MelReconstructionLoss (not in the reference); `g_loss` then reports the sum.  An attribute,
-        not a constructor argument: the constructor keeps the reference's signature (train.py:9-16)."""
+        backward(), e.g. loss.MelReconstructionLoss, loss.MultiResolutionSTFTLoss or a loss.SpectralLossSum of both (not
+        in the reference); `g_loss` then reports the sum.  A term with a `target(samples)` method has its real side
+        computed beside D(samples) on the real-path stream.  An attribute, not a constructor argument: the constructor
+        keeps the reference's signature (train.py:9-16)."""
         return self._spectral_loss
 
     @spectral_loss.setter
@@ -429,17 +431,17 @@ class GeneratorTrainer(_TrainerBase):
             main = torch.cuda.current_stream(samples.device)
             side = _graph.aux_stream(samples.device)
             side.wait_stream(main)
-            real_mel = None
+            real_target = None
             with _graph.forked(side), torch.no_grad():
                 r_features, r_score = self.discriminator(samples, features)
-                if isinstance(self.spectral_loss, MelReconstructionLoss):
-                    real_mel = self.spectral_loss.target(samples)
+                if callable(getattr(self.spectral_loss, "target", None)):     # any term that can precompute its real side
+                    real_target = self.spectral_loss.target(samples)
             fake = self.generator(features)
             f_features, f_score = self.discriminator(fake, features)
             main.wait_stream(side)
             loss = self.loss(r_features, f_features, r_score, f_score, gan_loss=self.sub_loss)
-            if real_mel is not None:
-                loss = loss + self.spectral_loss(fake, samples, target=real_mel)
+            if real_target is not None:
+                loss = loss + self.spectral_loss(fake, samples, target=real_target)
             elif self.spectral_loss is not None:
                 loss = loss + self.spectral_loss(fake, samples)
             loss.backward()
