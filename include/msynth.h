@@ -16,6 +16,14 @@
  *     caller-provided workspace (query its size with the *_workspace_bytes calls);
  *   - all work is enqueued on the caller's hipStream_t (passed as void*); no call
  *     synchronises the device, so every call is hipGraph-capture safe;
+ *   - memory contract (tests/test_gpu_memcontract.py): a call writes nothing outside its outputs and the workspace bytes its
+ *     query returned, leaves its inputs untouched, writes every output element, and its results do not depend on what outputs
+ *     or workspace held before.  Placement: where an entry's comment asks for 16-byte alignment, another address is refused
+ *     with MS_ERR_INVALID_ARG and nothing is written; the operands DESIGN.md 2.1 lists (those of the conv / transposed-conv
+ *     dispatch, the parts calls and the stream kernels that the tests move) may sit at any 4-byte address and are handled or
+ *     refused with a status.  Every other tensor -- x / y / t / gradients of the fused atoms and stack, x / y / gy / gx of the
+ *     weight-image kernels and of the 4 x 4 grouped layer -- is expected 16-byte aligned, as torch's allocator places it
+ *     (not tested by the launchers);
  *   - return value: MS_OK (0) or a negative ms_status; nothing is thrown;
  *   - re-entrant; no global state.
  */
@@ -175,6 +183,8 @@ int ms_conv1d_bwd_weight_multi(const ms_wgrad_multi_desc* d, void* workspace, si
  *   ms_residual_atom_supported   1 when the fused kernel takes this geometry (C in {32, 64, 128, 256}, L % 4 == 0,
  *                                dil <= 9), else 0: the caller then issues the two convs
  * b0, b1 and image must be 16-byte aligned.
+ * Every *_image_bytes / *_img_bytes size in this header covers the larger of the two piece schemes: a pack writes the part its
+ * scheme's kernels read (and nothing behind the size), not necessarily every byte of the buffer.
  */
 typedef struct ms_atom_desc {
     int32_t B, C, L, dil;
@@ -315,7 +325,8 @@ typedef struct ms_convt1d_desc {
 
 int ms_convt1d_out_len(const ms_convt1d_desc* d);
 
-/* y = act(conv_transpose1d(x, w) + bias).  Replaces generator/full.py:27-28,31-32,35-36,39-40. */
+/* y = act(conv_transpose1d(x, w) + bias).  Replaces generator/full.py:27-28,31-32,35-36,39-40.
+ * Operands at any 4-byte address are taken (a y that is not 16-byte aligned runs on the dword kernel). */
 int ms_convt1d_fwd(const ms_convt1d_desc* d, const float* x, const float* w, const float* bias,
                    float* y, void* workspace, size_t workspace_bytes, ms_stream_t stream);
 /* gx = conv_transpose1d_backward_input(gy * act'(y_act), w) */

@@ -342,7 +342,8 @@ Plan convt_plan(const ms_convt1d_desc* d, const ConvP& p, int which) {
     if (which == 0) {
         if (mst_convt1_applicable(p)) return pl.add(TF_THIN, p);            // one output channel: a stream
         if (mss_convt_applicable(d)) pl.add(TF_LANES, p, 0, UNSUPPORTED);    // inference batch: a weight stream
-        if (msm_convt_fwd_applicable(p)) return pl.add(TF_MFMA, p, msm_convt_fwd_ws(p));
+        // (its epilogue stores 8 / 16 bytes at a time: an output at a 4-byte address goes to the direct kernel)
+        if (msm_convt_fwd_applicable(p)) pl.add(TF_MFMA, p, msm_convt_fwd_ws(p), UNSUPPORTED);
         ConvP q = p;     // direct path: the loader modifier kind rides in q.act, the epilogue gets p.act
         q.act = p.in_act ? MS_MOD_LRELU_FWD : MS_ACT_NONE;
         return pl.add(TF_DIRECT, q);

@@ -1653,6 +1653,7 @@ int msm_conv1d_bwd_weight(const ConvP& p, const float* x, const float* x_act, in
 int msm_convt1d_fwd(const ConvP& p, const float* x, const float* w, const float* bias, float* y,
                     void* ws, size_t ws_bytes, hipStream_t s) {
     const int S = p.stride, CinT = p.Cout, CoutT = p.Cin, LinT = p.Lout;
+    if (((uintptr_t)y) & 15) return MS_ERR_UNSUPPORTED;      // (phase-interleaved epilogue: 8- / 16-byte stores to y)
     if (!ws || ws_bytes < msm_convt_fwd_ws(p) || (((uintptr_t)ws) & 15)) return MS_ERR_WORKSPACE;
     float* wp = (float*)ws;
     const size_t total = (size_t)CoutT * S * CinT * 3;
