@@ -285,9 +285,13 @@ int ms_conv1d_img_bwd_data(const ms_conv1d_desc* d, const float* gy, const float
 size_t ms_conv1d_workspace_bytes(const ms_conv1d_desc* d, int which);
 
 /* Name of the device kernel the dispatch selects for this geometry (which: 0 fwd, 1 bwd_data,
- * 2 bwd_weight) -- lets a profiler line be matched to a layer.  It describes a call without residual and
- * without y_act (a forward with either may run another kernel); "" when the dispatch has no kernel for the
- * geometry.  Static string, never NULL. */
+ * 2 bwd_weight) -- lets a profiler line be matched to a layer.  It describes a call whose operands are all 16-byte
+ * aligned, with the queried workspace, without residual and without a fused y_act output (a backward pass has its
+ * y_act input where the layer has an activation); a call that differs in one of these may run another kernel.  For
+ * the dense row-tile and im2col kernels (k_conv_rows3p / 3 / 2, k_conv_mfma_rows, k_igemm_*) the string is the exact
+ * template instantiation, the same text the launcher records in a profile session; for the other families the text
+ * before '<' is exact.  "" when the dispatch has no kernel for the geometry.  Thread-local string, never NULL, valid
+ * until the thread's next name query.  ms_convt1d_kernel_name: the same for the transposed conv. */
 const char* ms_conv1d_kernel_name(const ms_conv1d_desc* d, int which);
 
 /* Profiling aid (off by default; never needed for normal operation).  ms_profile_kernels(1) opens a profile session of the

@@ -26,6 +26,16 @@ void ms_note_kernel(int products, const char* fmt, ...) {
     g_prof_products = products;
 }
 
+bool ms_name_or_note(char* name, int products, const char* fmt, ...) {
+    if (!name && !g_prof_on) return false;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name ? name : g_prof_kernel, MS_PROFILE_NAME_MAX, fmt, ap);
+    va_end(ap);
+    if (!name) g_prof_products = products;
+    return name != nullptr;
+}
+
 bool ms_prof_on() { return g_prof_on != 0; }
 
 void ms_prof_add(hipEvent_t e0, hipEvent_t e1) {
@@ -352,7 +362,11 @@ Plan convt_plan(const ms_convt1d_desc* d, const ConvP& p, int which) {
         if (msm_convt_bwd_applicable(p)) return pl.add(TD_MFMA, p, msm_convt_bwd_data_ws(p));
         ConvP q = p;
         q.act = MS_ACT_NONE;
-        if (msm_fwd_applicable(q)) return pl.add(TD_CONV_MFMA, q, msm_fwd_ws(q));
+        if (msm_fwd_applicable(q)) {     // (this route's g.act is the kind of its activation OPERAND y_act: the conv has no epilogue)
+            const size_t ws = msm_fwd_ws(q);
+            q.act = p.act;
+            return pl.add(TD_CONV_MFMA, q, ws);
+        }
         return pl.add(TD_CONV_DIRECT, q);
     }
     // (every weight-gradient route also leaves the bias gradient's slice partials room at the workspace's tail;
@@ -412,7 +426,8 @@ const char* route_name(Kind k, const ConvP& g) {
     switch (k) {
         case F_THIN_SHORT: case F_THIN: return mst_fwd_name(g);
         case F_SMALL: return mss_conv_name(g);
-        case F_PAD4: case F_MFMA: case TD_CONV_MFMA: return msm_fwd_name(g);
+        case F_PAD4: case F_MFMA: return msm_fwd_name(g);
+        case TD_CONV_MFMA: { ConvP c = g; c.act = MS_ACT_NONE; return msm_fwd_name(c, g.act); }
         case F_G4: return msg4_parts_name(0);
         case F_G3: return msg3_fwd_name(g);
         case F_G: return msg_fwd_name(g);
@@ -763,8 +778,11 @@ int ms_convt1d_bwd_data(const ms_convt1d_desc* d, const float* gy, const float* 
     return run(convt_plan(d, p, 1), workspace, workspace_bytes, [&](Kind k, const ConvP& g) {
         switch (k) {
             case TD_MFMA: return msm_convt1d_bwd_data(g, gy, y_act, w, gx, workspace, workspace_bytes, s);
-            case TD_CONV_MFMA:
-                return msm_conv1d_fwd(g, gy, y_act, p.act, w, nullptr, nullptr, gx, nullptr, workspace, workspace_bytes, s);
+            case TD_CONV_MFMA: {
+                ConvP c = g;
+                c.act = MS_ACT_NONE;
+                return msm_conv1d_fwd(c, gy, y_act, g.act, w, nullptr, nullptr, gx, nullptr, workspace, workspace_bytes, s);
+            }
             default: return msk_conv1d_fwd_direct(g, gy, y_act, p.act, w, nullptr, nullptr, gx, nullptr, s);
         }
     });
@@ -813,7 +831,9 @@ size_t ms_convt1d_workspace_bytes(const ms_convt1d_desc* d, int which) {
 
 const char* ms_convt1d_kernel_name(const ms_convt1d_desc* d, int which) {
     ConvP p;
-    return make_convt(d, &p) && which >= 0 && which <= 2 ? route_name(convt_plan(d, p, which).r[0].kind, p) : "";
+    if (!make_convt(d, &p) || which < 0 || which > 2) return "";
+    const Plan pl = convt_plan(d, p, which);
+    return route_name(pl.r[0].kind, pl.r[0].g);
 }
 
 }  // extern "C"

@@ -13,6 +13,9 @@ size_t msm_bwd_weight_ws(const ConvP& p);
 size_t msm_convt_fwd_ws(const ConvP& p);
 
 const char* msm_fwd_name(const ConvP& p);
+// ... with an activation operand of the given derivative kind in place of the descriptor's in_act (0: none); the transposed
+// conv's backward data through the conv kernels passes y_act that way
+const char* msm_fwd_name(const ConvP& p, int x_act_kind);
 const char* msm_bwd_data_name(const ConvP& p);
 const char* msm_bwd_weight_name(const ConvP& p);
 const char* msm_convt_fwd_name(const ConvP& p);

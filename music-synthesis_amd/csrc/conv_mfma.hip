@@ -995,9 +995,24 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------ host side
+// The dispatch inside the family is a plan, like api.hip's one level up.  One planner per pass (plan_fwd, plan_bwd_data,
+// plan_convt_fwd, plan_convt_bwd_data; plan_wgrad / plan_convt_wgrad for the two im2col weight gradients) decides, once, the
+// kernel family and tile, the split-K depth, the weight re-layout in front, the grid and the workspace layout.  It has three
+// readers and nothing else decides anything: msm_*_ws returns the plan's bytes, msm_*_name asks the plan's launcher for the
+// spelling of what it would launch, msm_* runs the plan.  What depends on the call and not on the geometry -- where the
+// operands and the workspace sit -- is the planners' explicit input (RowCall); the queries plan with its defaults.
 bool dense_same(const ConvP& p) {
     return p.groups == 1 && p.stride == 1 && p.Lout == p.Lin && (p.K == 1 || p.K == 3 || p.K == 5 || p.K == 7) &&
            (long long)p.B * p.Lin < (1LL << 31) && (long long)p.Cin * p.K < (1 << 30);
+}
+
+bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }   // (an absent operand counts as aligned)
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+dim3 blocks256(size_t n, unsigned cap) {
+    n = (n + 255) / 256;
+    return dim3(n > cap ? cap : (unsigned)n);
 }
 
 enum Cfg { CFG_128x128, CFG_64x64, CFG_32x256, CFG_32x128 };
@@ -1015,29 +1030,35 @@ void cfg_tile(Cfg c, int* bm, int* bn) {
     else { *bm = 32; *bn = 256; }
 }
 
+// name (here and in every launcher below): not null = a name query, see ms_name_or_note (ms_common.h)
 template <int K, bool TRANS>
 int launch_conv_k(Cfg cfg, const IgP& p, const float* X, const float* Xact, const float* W,
-                  const float* bias, const float* res, float* Y, float* Yact, hipStream_t s) {
+                  const float* bias, const float* res, float* Y, float* Yact, hipStream_t s, char* name) {
     int bm, bn;
     cfg_tile(cfg, &bm, &bn);
     dim3 grid((unsigned)((p.N + bn - 1) / bn), (unsigned)((p.M + bm - 1) / bm));
-    if (cfg == CFG_128x128)
-        hipLaunchKernelGGL((k_igemm_conv<2, 2, 2, 2, K, TRANS>), grid, dim3(256), 0, s, p, X, Xact, W, bias, res, Y, Yact);
-    else if (cfg == CFG_64x64)
-        hipLaunchKernelGGL((k_igemm_conv<2, 2, 1, 1, K, TRANS>), grid, dim3(256), 0, s, p, X, Xact, W, bias, res, Y, Yact);
-    else
-        hipLaunchKernelGGL((k_igemm_conv<1, 4, 1, 2, K, TRANS>), grid, dim3(256), 0, s, p, X, Xact, W, bias, res, Y, Yact);
+#define MS_IG(WGM, WGN, TM, TN)                                                                                            \
+    do {                                                                                                                   \
+        if (ms_name_or_note(name, 0, "k_igemm_conv<%d, %d, %d, %d, %d, %s>", WGM, WGN, TM, TN, K, TRANS ? "true" : "false")) \
+            return MS_OK;                                                                                                  \
+        hipLaunchKernelGGL((k_igemm_conv<WGM, WGN, TM, TN, K, TRANS>), grid, dim3(256), 0, s, p, X, Xact, W, bias, res, Y, \
+                           Yact);                                                                                          \
+    } while (0)
+    if (cfg == CFG_128x128) MS_IG(2, 2, 2, 2);
+    else if (cfg == CFG_64x64) MS_IG(2, 2, 1, 1);
+    else MS_IG(1, 4, 1, 2);
+#undef MS_IG
     MS_CHECK_LAUNCH();
     return MS_OK;
 }
 
 template <bool TRANS>
 int launch_conv(int K, Cfg cfg, const IgP& p, const float* X, const float* Xact, const float* W,
-                const float* bias, const float* res, float* Y, float* Yact, hipStream_t s) {
-    if (K == 1) return launch_conv_k<1, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-    if (K == 3) return launch_conv_k<3, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-    if (K == 5) return launch_conv_k<5, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-    if (K == 7) return launch_conv_k<7, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
+                const float* bias, const float* res, float* Y, float* Yact, hipStream_t s, char* name) {
+    if (K == 1) return launch_conv_k<1, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s, name);
+    if (K == 3) return launch_conv_k<3, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s, name);
+    if (K == 5) return launch_conv_k<5, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s, name);
+    if (K == 7) return launch_conv_k<7, TRANS>(cfg, p, X, Xact, W, bias, res, Y, Yact, s, name);
     return MS_ERR_UNSUPPORTED;
 }
 
@@ -1050,8 +1071,6 @@ struct WgradPlan {
 WgradPlan plan_wgrad(const ConvP& p) {
     WgradPlan q;
     const int NG = p.Cin * p.K;
-    const int t128 = ms_ceil_div(p.Cout, 128) * ms_ceil_div(NG, 128);
-    (void)t128;
     if (p.Cout <= 32) q.cfg = NG <= 128 ? CFG_32x128 : CFG_32x256;
     else if (p.Cout >= 128 && NG >= 128) q.cfg = CFG_128x128;   // 4 MFMAs per 4 LDS fragment reads
     else q.cfg = CFG_64x64;
@@ -1073,19 +1092,44 @@ WgradPlan plan_wgrad(const ConvP& p) {
     return q;
 }
 
+// the im2col weight-gradient GEMM of a plan: M x NG tiles, pl.nsplit slabs.  v4: the 16-byte loader (rows that are a multiple
+// of 4 long, zero padding, 16-byte aligned operands)
+int launch_wgrad(const WgradPlan& pl, int K, bool v4, const IgP& q, const float* A, const float* Aact, const float* Bm,
+                 const float* Bact, int bkind, float* partial, hipStream_t s, char* name) {
+    dim3 grid((unsigned)ms_ceil_div(q.KG, pl.bn), (unsigned)ms_ceil_div(q.M, pl.bm), (unsigned)pl.nsplit);
+#define MS_WG1(KERNEL, WGM, WGN, TM, TN, KK)                                                                      \
+    do {                                                                                                          \
+        if (ms_name_or_note(name, 0, #KERNEL "<%d, %d, %d, %d, %d>", WGM, WGN, TM, TN, KK)) return MS_OK;           \
+        hipLaunchKernelGGL((KERNEL<WGM, WGN, TM, TN, KK>), grid, dim3(256), 0, s, q, pl.cps, A, Aact, Bm, Bact,    \
+                           bkind, partial, pl.stride_floats);                                                     \
+    } while (0)
+#define MS_WG(WGM, WGN, TM, TN, KK)                           \
+    do {                                                      \
+        if (v4) MS_WG1(k_igemm_wgrad_v4, WGM, WGN, TM, TN, KK); \
+        else MS_WG1(k_igemm_wgrad, WGM, WGN, TM, TN, KK);       \
+    } while (0)
+#define MS_WG_K(KK)                                           \
+    do {                                                      \
+        if (pl.cfg == CFG_128x128) MS_WG(2, 2, 2, 2, KK);     \
+        else if (pl.cfg == CFG_64x64) MS_WG(2, 2, 1, 1, KK);  \
+        else if (pl.cfg == CFG_32x128) MS_WG(1, 4, 1, 1, KK); \
+        else MS_WG(1, 4, 1, 2, KK);                           \
+    } while (0)
+    if (K == 1) MS_WG_K(1);
+    else if (K == 3) MS_WG_K(3);
+    else if (K == 5) MS_WG_K(5);
+    else if (K == 7) MS_WG_K(7);
+    else if (K == 15) MS_WG_K(15);
+    else return MS_ERR_UNSUPPORTED;
+#undef MS_WG_K
+#undef MS_WG
+#undef MS_WG1
+    MS_CHECK_LAUNCH();
+    return MS_OK;
+}
 
 // ---- row-tile kernel dispatch
 enum RowCfg { ROW_128x128, ROW_64x128, ROW_64x64, ROW_32x256, ROW_64x256 };
-
-const char* row_tile_str(RowCfg c) {
-    switch (c) {
-        case ROW_128x128: return "2, 2, 2, 2";
-        case ROW_64x128: return "2, 2, 1, 2";
-        case ROW_64x64: return "2, 2, 1, 1";
-        case ROW_64x256: return "1, 4, 2, 2";
-        default: return "1, 4, 1, 2";
-    }
-}
 
 constexpr int row_cc(int K) { return K == 7 ? 4 : (K == 1 ? 32 : 8); }
 
@@ -1147,200 +1191,14 @@ bool make_rowp(RowP* q, RowCfg cfg, int B, int CK, int L, int M, int K, int dil,
 // deep contractions (>= 128 input channels) stage two channel chunks per barrier pair
 bool row_deep(int K, int CK) { return K != 7 && K != 1 && CK >= 128 && CK % (2 * row_cc(K)) == 0; }
 
-// Does a row-tile launch go to the pipelined kernel of conv_rows2.hip?  (16-byte aligned operands,
-// zero padding, plain input rows, activation handling it knows; backward data additionally needs
-// the forward-layout weights, which it reads directly.)
-bool rows2_pick(RowCfg cfg, int K, int CC, bool has_act, int epi_s, int in_s, const RowP& p, const float* X,
-                const float* Xact, const float* W, const float* res, const float* Y, const float* Yact,
-                Row2P* q, int* tile, int* am, int* in_s_out = nullptr) {
-    if (in_s_out) *in_s_out = in_s;
-    if (p.pad_mode != MS_PAD_ZERO || cfg == ROW_64x256) return false;
-    if (has_act && p.in_act != MS_ACT_LRELU && p.in_act != MS_ACT_NONE && p.in_act != MS_MOD_LRELU_FWD) return false;
-    *am = (has_act && p.in_act == MS_ACT_LRELU) ? (in_s == 1 ? 1 : 2) : 0;
-    if (has_act && p.in_act == MS_MOD_LRELU_FWD) *am = 3;      // LeakyReLU in front of the conv, on load
-    if (in_s != 1 && *am != 2 && *am != 0) return false;
-    const float* Wuse = *am == 1 ? p.Wfwd : W;
-    if (!Wuse || (*am == 1 && p.M % 4)) return false;
-    if (((((uintptr_t)X) | ((uintptr_t)Wuse) | ((uintptr_t)(Xact ? Xact : X)) | ((uintptr_t)Y) |
-          ((uintptr_t)(Yact ? Yact : Y)) | ((uintptr_t)(res ? res : X))) & 15) != 0)
-        return false;
-    if ((long long)p.B * p.CK * p.L >= (1LL << 31) || (long long)p.M * p.KG >= (1LL << 31)) return false;
-    q->B = p.B; q->CK = p.CK; q->L = p.L; q->M = p.M; q->dil = p.dil; q->off0 = p.off0; q->act = p.act;
-    q->KG = p.KG; q->Lt = p.Lt; q->R = p.R; q->SS = p.SS; q->RSZ = p.RSZ; q->tiles_per_row = p.tiles_per_row;
-    q->PX = p.RSZ; q->CKs = p.CKs; q->zstride = p.zstride; q->slope = p.slope; q->scratch_off = 0;
-    *tile = cfg == ROW_128x128 ? MSR2_128x128 : (cfg == ROW_64x128 ? MSR2_64x128 :
-            (cfg == ROW_64x64 ? MSR2_64x64 : MSR2_32x256));
-    if (in_s == 1 && msr3_supported(*tile, K, *am, epi_s, *q, 1)) return true;   // split-bf16 kernel: rows of any length
-    // short rows of a length that is not a multiple of 4 (k5 conv at L = 17 / 9): whole-row staging
-    if (in_s == 1 && in_s_out && K == 5 && p.tiles_per_row == 1 && p.Lt == p.L) {
-        int bm, bn;
-        row_tile(cfg, &bm, &bn);
-        if (p.L < bn && p.L % 4 != 0 && msr2_supported(*tile, K, CC, *am, epi_s, *q, 0)) {
-            *in_s_out = 0;
-            return true;
-        }
-    }
-    return msr3_supported(*tile, K, *am, epi_s, *q, in_s) || msr2_supported(*tile, K, CC, *am, epi_s, *q, in_s);
-}
+int rows_cc_eff(int K, int CK) { return row_cc(K) * (row_deep(K, CK) ? 2 : 1); }
 
-// Paired eight-wave split-bf16 kernel (k_conv_rows3p): rows per workgroup (128 / 64) when the launch should take
-// it -- supported and its grid (half as many, twice as wide workgroups) still fills most of the 256 CUs -- else 0.
-int rows3p_bm(const Row2P& q, int bn, int K, int am, int epi_s, int in_s, unsigned gz) {
-    if (bn != 128) return 0;                     // (q's tiling must be the 128-column one the kernel's groups own)
-    constexpr int min_wgs = 128;
-    const long long ntiles = q.R == 1 ? (long long)q.B * q.tiles_per_row : (q.B + q.R - 1) / q.R;
-    // (C = 256 at L = 256, B = 32: 64 workgroups of 128 rows or 128 of 64 rows both measured slower than the
-    //  four-wave kernel's 256 workgroups: 61 / 44 vs 30 us -- no fallback to narrower workgroups)
-    const int bm = (q.M >= 128 && K == 3) ? 128 : (q.M <= 32 ? 32 : 64);
-    if (!msr3p_supported(bm, K, am, epi_s, q, in_s)) return 0;
-    const long long wgs = ((ntiles + 1) / 2) * ((q.M + bm - 1) / bm) * gz;
-    return wgs >= min_wgs ? bm : 0;
-}
-
-// ... and for the transposed-conv forward (two-tap form, conv_rows3.hip HS): 128 rows where that still fills the chip
-int rows3p_convt_bm(const Row2P& q, int bn, int S, unsigned gz) {
-    if (bn != 128) return 0;
-    constexpr int min_wgs = 128;
-    const long long ntiles = q.R == 1 ? (long long)q.B * q.tiles_per_row : (q.B + q.R - 1) / q.R;
-    for (int bm = 128; bm >= 64; bm >>= 1) {
-        if (q.M < bm || !msr3p_convt_supported(bm, S, q)) continue;
-        if (((ntiles + 1) / 2) * ((q.M + bm - 1) / bm) * gz >= min_wgs) return bm;
-    }
-    return 0;
-}
-
-Row2P rows3p_retile(const Row2P& q, int K) {
-    Row2P r = q;
-    r.Lt = 128;
-    r.tiles_per_row = (q.L + 127) / 128;
-    r.SS = 128 + (K - 1) * q.dil;
-    r.RSZ = r.SS;
-    r.PX = r.SS;
-    return r;
-}
-
-template <int K, bool HAS_ACT, int EPI_S = 0, int IN_S = 1, int CCMUL = 1>
-int launch_rows_k(RowCfg cfg, const RowP& p, const float* X, const float* Xact, const float* W,
-                  const float* bias, const float* res, float* Y, float* Yact, hipStream_t s) {
-    constexpr int CC = row_cc(K) * CCMUL;
-    int bm, bn;
-    row_tile(cfg, &bm, &bn);
-    const unsigned gx = p.R == 1 ? (unsigned)(p.B * p.tiles_per_row) : (unsigned)((p.B + p.R - 1) / p.R);
-    dim3 grid(gx, (unsigned)((p.M + bm - 1) / bm), (unsigned)((p.CK + p.CKs - 1) / p.CKs));
-    // pipelined second-generation kernel where its requirements hold (conv_rows2.hip)
-    {
-        Row2P q;
-        int tile, am, in_s_eff;
-        if (rows2_pick(cfg, K, CC, HAS_ACT, EPI_S, IN_S, p, X, Xact, W, res, Y, Yact, &q, &tile, &am, &in_s_eff)) {
-            if (const int bmp = rows3p_bm(q, bn, K, am, EPI_S, in_s_eff, grid.z))
-                return msr3p_launch(bmp, K, am, q, X, Xact, am == 1 ? p.Wfwd : W, bias, res, Y, Yact, grid.z, s);
-            if (cfg == ROW_32x256 && q.R == 1 && q.Lt == 256) {      // 32-channel layers: the same rows as 128-column tiles
-                Row2P q2 = rows3p_retile(q, K);
-                if (const int bmp = rows3p_bm(q2, 128, K, am, EPI_S, in_s_eff, grid.z))
-                    return msr3p_launch(bmp, K, am, q2, X, Xact, am == 1 ? p.Wfwd : W, bias, res, Y, Yact, grid.z, s);
-            }
-            if (msr3_supported(tile, K, am, EPI_S, q, in_s_eff))      // split-bf16 matrix pipe (conv_rows3.hip)
-                return msr3_launch(tile, K, am, q, X, Xact, am == 1 ? p.Wfwd : W, bias, res, Y, Yact, grid.x, grid.y,
-                                   grid.z, s);
-            return msr2_launch(tile, K, CC, am, EPI_S, q, X, Xact, am == 1 ? p.Wfwd : W, bias, res, Y, Yact, grid.x,
-                               grid.y, grid.z, s, in_s_eff);
-        }
-    }
-    const size_t lds = (size_t)(bm * (CC * K + 1) + CC * p.RSZ) * sizeof(float);
-    if (lds > 64 * 1024) return MS_ERR_UNSUPPORTED;
-    switch (cfg) {
-        case ROW_128x128:
-            hipLaunchKernelGGL((k_conv_mfma_rows<2, 2, 2, 2, K, CC, HAS_ACT, EPI_S, IN_S>), grid, dim3(256), lds, s, p, X, Xact, W, bias, res, Y, Yact);
-            break;
-        case ROW_64x128:
-            hipLaunchKernelGGL((k_conv_mfma_rows<2, 2, 1, 2, K, CC, HAS_ACT, EPI_S, IN_S>), grid, dim3(256), lds, s, p, X, Xact, W, bias, res, Y, Yact);
-            break;
-        case ROW_64x64:
-            hipLaunchKernelGGL((k_conv_mfma_rows<2, 2, 1, 1, K, CC, HAS_ACT, EPI_S, IN_S>), grid, dim3(256), lds, s, p, X, Xact, W, bias, res, Y, Yact);
-            break;
-        case ROW_64x256:
-            hipLaunchKernelGGL((k_conv_mfma_rows<1, 4, 2, 2, K, CC, HAS_ACT, EPI_S, IN_S>), grid, dim3(256), lds, s, p, X, Xact, W, bias, res, Y, Yact);
-            break;
-        default:
-            hipLaunchKernelGGL((k_conv_mfma_rows<1, 4, 1, 2, K, CC, HAS_ACT, EPI_S, IN_S>), grid, dim3(256), lds, s, p, X, Xact, W, bias, res, Y, Yact);
-            break;
-    }
-    MS_CHECK_LAUNCH();
-    return MS_OK;
-}
-
-int launch_rows(int K, RowCfg cfg, const RowP& p, const float* X, const float* Xact, const float* W,
-                const float* bias, const float* res, float* Y, float* Yact, hipStream_t s) {
-    const bool deep = row_deep(K, p.CK);
-#define MS_ROWS(KK, ACT)                                                                              \
-    (deep ? launch_rows_k<KK, ACT, 0, 1, 2>(cfg, p, X, Xact, W, bias, res, Y, Yact, s)                \
-          : launch_rows_k<KK, ACT, 0, 1, 1>(cfg, p, X, Xact, W, bias, res, Y, Yact, s))
-    if (Xact) {
-        if (K == 1) return launch_rows_k<1, true>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-        if (K == 3) return MS_ROWS(3, true);
-        if (K == 5) return MS_ROWS(5, true);
-        if (K == 7) return launch_rows_k<7, true>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-    } else {
-        if (K == 1) return launch_rows_k<1, false>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-        if (K == 3) return MS_ROWS(3, false);
-        if (K == 5) return MS_ROWS(5, false);
-        if (K == 7) return launch_rows_k<7, false>(cfg, p, X, Xact, W, bias, res, Y, Yact, s);
-    }
-#undef MS_ROWS
-    return MS_ERR_UNSUPPORTED;
-}
-
-// name of the kernel a row-tile launch resolves to (16-byte aligned tensors assumed): the pipelined
-// second generation where its requirements hold (conv_rows2.hip), else the first
-const char* row_kname(RowCfg c, int K, bool act, int CK, int L = 0, int R = 1, int SS = 0, int pad_mode = MS_PAD_ZERO,
-                      int in_act = MS_ACT_LRELU, int epi_s = 0, int B = 0, int M = 0) {
-    static thread_local char buf[96];
-    const char* tile = row_tile_str(c);
-    const int CC = epi_s ? row_cc(K) : row_cc(K) * (row_deep(K, CK) ? 2 : 1);
-    const int am = (act && in_act == MS_ACT_LRELU) ? 1 : 0;
-    if (L > 0 && c != ROW_64x256 && pad_mode == MS_PAD_ZERO && (!act || in_act == MS_ACT_LRELU || in_act == MS_ACT_NONE)) {
-        Row2P q;
-        q.L = L; q.R = R; q.SS = SS;
-        const int t2 = c == ROW_128x128 ? MSR2_128x128 : (c == ROW_64x128 ? MSR2_64x128 : (c == ROW_64x64 ? MSR2_64x64 : MSR2_32x256));
-        int bm, bn;
-        row_tile(c, &bm, &bn);
-        {
-            Row2P h = q;
-            h.B = B; h.M = M > 0 ? M : 64; h.CK = CK; h.CKs = CK; h.PX = R * SS; h.Lt = L >= bn ? bn : L;
-            h.tiles_per_row = L >= bn ? (L + bn - 1) / bn : 1;
-            h.dil = K > 1 ? (SS - h.Lt) / (K - 1) : 1;        // SS = Lt + (K - 1) dil (rows3p_retile rebuilds it)
-            if (h.dil < 1) h.dil = 1;
-            if (const int bmp = B > 0 ? rows3p_bm(h, bn, K, am, epi_s, 1, 1) : 0) {
-                snprintf(buf, sizeof(buf), "k_conv_rows3p<%s, %d, %d>", bmp == 128 ? "2, 2, 2" : (bmp == 64 ? "2, 1, 2" : "1, 1, 1"), K, am);
-                return buf;
-            }
-            if (c == ROW_32x256 && R == 1 && L >= 256 && B > 0) {
-                Row2P h2 = h;
-                h2.Lt = 256;
-                h2 = rows3p_retile(h2, K);
-                if (const int bmp = rows3p_bm(h2, 128, K, am, epi_s, 1, 1)) {
-                    snprintf(buf, sizeof(buf), "k_conv_rows3p<%s, %d, %d>", bmp == 128 ? "2, 2, 2" : (bmp == 64 ? "2, 1, 2" : "1, 1, 1"), K, am);
-                    return buf;
-                }
-            }
-            if (msr3_supported(t2, K, am, epi_s, h)) {
-                snprintf(buf, sizeof(buf), "k_conv_rows3<%s, %d, %d, %s>", tile, K, am,
-                         (L % 4 == 0 && h.Lt % 4 == 0) ? "true" : "false");
-                return buf;
-            }
-        }
-        if (K == 5 && CC == 16 && epi_s == 0 && am == 1 && L < bn && L % 4 != 0 && c != ROW_32x256) {   // short-row mode
-            snprintf(buf, sizeof(buf), "k_conv_rows2<%s, 5, 16, %d, 0, 0>", tile, am);
-            return buf;
-        }
-        if (msr2_supported(t2, K, CC, am, epi_s, q)) {
-            snprintf(buf, sizeof(buf), "k_conv_rows2<%s, %d, %d, %d, %d>", tile, K, CC, am, epi_s);
-            return buf;
-        }
-    }
-    if (epi_s) snprintf(buf, sizeof(buf), "k_conv_mfma_rows<%s, 3, 8, false, %d, 1>", tile, epi_s);
-    else snprintf(buf, sizeof(buf), "k_conv_mfma_rows<%s, %d, %d, %s, 0, 1>", tile, K, CC, act ? "true" : "false");
-    return buf;
+bool rows_ok(const ConvP& p, bool bwd) {
+    const int M = bwd ? p.Cin : p.Cout, CK = bwd ? p.Cout : p.Cin;
+    if (!rows_applicable(M, CK, p.K, p.Lin)) return false;
+    if (((size_t)CK * p.K) % 4) return false;
+    RowP q;
+    return make_rowp(&q, pick_row_cfg(M, p.B, p.Lin), p.B, CK, p.Lin, M, p.K, p.dil, 0, 0, 0, 0, 0.f);
 }
 
 // ---- split-K for row-tile launches whose (M, N) tiling alone leaves most of the 256 CUs idle
@@ -1352,11 +1210,9 @@ struct RowSplit {
     size_t out_floats;
 };
 
-int rows_wgs(RowCfg cfg, const RowP& p) {
-    int bm, bn;
-    row_tile(cfg, &bm, &bn);
-    const int gx = p.R == 1 ? p.B * p.tiles_per_row : (p.B + p.R - 1) / p.R;
-    return gx * ((p.M + bm - 1) / bm);
+dim3 rows_grid(int bm, const RowP& p) {
+    return dim3(p.R == 1 ? (unsigned)(p.B * p.tiles_per_row) : (unsigned)((p.B + p.R - 1) / p.R),
+                (unsigned)((p.M + bm - 1) / bm), (unsigned)((p.CK + p.CKs - 1) / p.CKs));
 }
 
 int split_max_wgs() {
@@ -1366,7 +1222,10 @@ int split_max_wgs() {
 RowSplit plan_rows_split(RowCfg cfg, const RowP& p, int CC) {
     RowSplit q;
     q.ns = 1; q.cks = p.CK; q.out_floats = (size_t)p.B * p.M * p.L;
-    const int wgs = rows_wgs(cfg, p);
+    int bm, bn;
+    row_tile(cfg, &bm, &bn);
+    const dim3 g = rows_grid(bm, p);
+    const int wgs = (int)(g.x * g.y);
     const int nchunks = p.CK / CC;
     // (one workgroup per CU is still under-filled when the contraction is long enough to amortise the
     // slab pass: the 1024 -> 1024 k5 conv at B*L = 2048 has 256 tiles and 64 chunks)
@@ -1391,51 +1250,377 @@ RowSplit plan_rows_split(RowCfg cfg, const RowP& p, int CC) {
     return q;
 }
 
-size_t rows_split_ws(RowCfg cfg, const RowP& p, int CC) {
-    const RowSplit q = plan_rows_split(cfg, p, CC);
-    return q.ns > 1 ? (size_t)q.ns * q.out_floats * sizeof(float) : 0;
+// Paired eight-wave split-bf16 kernel (k_conv_rows3p): rows per workgroup (128 / 64) when the launch should take
+// it -- supported and its grid (half as many, twice as wide workgroups) still fills most of the 256 CUs -- else 0.
+int rows3p_bm(const Row2P& q, int bn, int K, int am, int epi_s, int in_s, unsigned gz) {
+    if (bn != 128) return 0;                     // (q's tiling must be the 128-column one the kernel's groups own)
+    constexpr unsigned min_wgs = 128;
+    // (C = 256 at L = 256, B = 32: 64 workgroups of 128 rows or 128 of 64 rows both measured slower than the
+    //  four-wave kernel's 256 workgroups: 61 / 44 vs 30 us -- no fallback to narrower workgroups)
+    const int bm = (q.M >= 128 && K == 3) ? 128 : (q.M <= 32 ? 32 : 64);
+    if (!msr3p_supported(bm, K, am, epi_s, q, in_s)) return 0;
+    const dim3 g = msr3p_grid(bm, q, gz);
+    return (unsigned long long)g.x * g.y * g.z >= min_wgs ? bm : 0;
 }
 
-// launch(rowp, bias, res, Y, Yact) runs the row-tile kernel; nch / rowlen describe the bias index
-template <class F>
-int rows_maybe_split(RowCfg cfg, const RowP& r, int CC, int nch, int rowlen, const float* bias,
-                     const float* res, float* Y, float* Yact, void* slab_ws, size_t slab_bytes,
-                     hipStream_t s, F launch) {
-    const RowSplit q = plan_rows_split(cfg, r, CC);
-    if (q.ns <= 1 || !slab_ws || slab_bytes < (size_t)q.ns * q.out_floats * sizeof(float))
-        return launch(r, bias, res, Y, Yact);
-    RowP z = r;
-    z.CKs = q.cks; z.zstride = (long long)q.out_floats; z.act = MS_ACT_NONE;
-    float* slabs = (float*)slab_ws;
-    const int rc = launch(z, (const float*)nullptr, (const float*)nullptr, slabs, (float*)nullptr);
-    if (rc != MS_OK) return rc;
-    unsigned nb = (unsigned)((q.out_floats + 255) / 256);
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(k_rows_split_finish, dim3(nb), dim3(256), 0, s, slabs, q.ns, q.out_floats,
-                       bias, nch, rowlen, r.act, r.slope, res, Y, Yact, q.out_floats);
+// ... and for the transposed-conv forward (two-tap form, conv_rows3.hip HS): 128 rows where that still fills the chip
+int rows3p_convt_bm(const Row2P& q, int bn, int S, unsigned gz) {
+    if (bn != 128) return 0;
+    constexpr unsigned min_wgs = 128;
+    for (int bm = 128; bm >= 64; bm >>= 1) {
+        if (q.M < bm || !msr3p_convt_supported(bm, S, q)) continue;
+        const dim3 g = msr3p_grid(bm, q, gz);
+        if ((unsigned long long)g.x * g.y * g.z >= min_wgs) return bm;
+    }
+    return 0;
+}
+
+Row2P rows3p_retile(const Row2P& q, int K) {
+    Row2P r = q;
+    r.Lt = 128;
+    r.tiles_per_row = (q.L + 127) / 128;
+    r.SS = 128 + (K - 1) * q.dil;
+    r.RSZ = r.SS;
+    r.PX = r.SS;
+    return r;
+}
+
+// What a row-tile plan depends on besides the geometry: where the call's operands and its workspace sit.  The defaults are
+// what the queries plan with: every operand 16-byte aligned (an absent one counts as aligned), the queried workspace present.
+struct RowCall {
+    bool x16 = true, xact16 = true, w16 = true, res16 = true, y16 = true, yact16 = true;
+    bool ws = true, ws16 = true;
+    size_t ws_bytes = ~(size_t)0;
+};
+
+RowCall row_call(const float* x, const float* xact, const float* w, const float* res, const float* y, const float* yact,
+                 const void* ws, size_t ws_bytes) {
+    RowCall c;
+    c.x16 = al16(x); c.xact16 = al16(xact); c.w16 = al16(w); c.res16 = al16(res); c.y16 = al16(y); c.yact16 = al16(yact);
+    c.ws = ws != nullptr; c.ws16 = al16(ws); c.ws_bytes = ws_bytes;
+    return c;
+}
+
+struct RowPlan {
+    enum Fam { IGEMM, ROWS1, ROWS2, ROWS3, ROWS3P, ROWS3P_T } fam = IGEMM;   // k_igemm_conv, k_conv_mfma_rows, k_conv_rows2 / 3 / 3p
+    enum Pack { PACK_NONE, FLIP_W, PACK_T, PACK_T2, PACK_TB, PACK_TB2 } pack = PACK_NONE;   // weight re-layout kernel in front
+    Cfg icfg = CFG_64x64;      // IGEMM: its tile
+    RowCfg cfg = ROW_64x64;    // the row tile; tile: its MSR2_* name; bmp: rows per workgroup of the paired kernels
+    int tile = 0, bmp = 0;
+    int K = 0, CC = 0;         // taps and channels per chunk the kernel is instantiated for
+    bool has_act = false;      // an activation operand rides along (Xact)
+    int am = 0, epi_s = 0, in_s = 1;   // act_mode of conv_rows2.h, phase-interleaving epilogue, phase-split input (0: whole short rows)
+    RowP r;                    // the rows, split applied (CKs, zstride, act = NONE)
+    Row2P q;                   // the same for the pipelined kernels (the paired ones: retiled to 128 columns where needed)
+    int ns = 1;                // split-K slices (grid.z), each a raw slab of out_floats
+    size_t out_floats = 0;
+    int act = 0, nch = 0, rowlen = 0;   // epilogue of the slab sum: activation, bias index
+    dim3 grid;
+    size_t wbytes = 0, bytes = 0;       // workspace: [re-laid-out weights | slabs]; bytes: all of it, the query's answer
+};
+
+// One row-tile launch decided once.  r0: the rows before any split.  K: taps of the window; conv_t: a transposed-conv pass
+// (K = 3, single chunks; its pipelined kernels multiply only the two live taps of each phase), pair_t: its forward, which the
+// paired split-bf16 kernel takes.  wbytes: re-laid-out weights in front of the workspace (the kernel's W operand, unless act_mode 1
+// reads the forward layout: wfwd says the call has it).
+RowPlan plan_rows(RowCfg cfg, const RowP& r0, int K, bool has_act, int epi_s, int in_s, bool conv_t, bool pair_t,
+                  size_t wbytes, bool wfwd, int nch, int rowlen, const RowCall& c) {
+    RowPlan pl;
+    pl.fam = RowPlan::ROWS1; pl.cfg = cfg; pl.r = r0; pl.has_act = has_act; pl.epi_s = epi_s; pl.in_s = in_s;
+    pl.K = K; pl.CC = conv_t ? row_cc(K) : rows_cc_eff(K, r0.CK);
+    pl.act = r0.act; pl.nch = nch; pl.rowlen = rowlen; pl.wbytes = wbytes;
+    int bm, bn;
+    row_tile(cfg, &bm, &bn);
+    // split-K where the workspace passed has room for the slabs
+    const RowSplit sp = plan_rows_split(cfg, r0, pl.CC);
+    const size_t slabs = sp.ns > 1 ? (size_t)sp.ns * sp.out_floats * sizeof(float) : 0;
+    pl.out_floats = sp.out_floats;
+    pl.bytes = wbytes + slabs;
+    bool out16 = c.y16 && c.yact16 && c.res16;
+    if (slabs && c.ws && c.ws_bytes >= pl.bytes) {
+        pl.ns = sp.ns;
+        pl.r.CKs = sp.cks; pl.r.zstride = (long long)sp.out_floats; pl.r.act = MS_ACT_NONE;
+        out16 = c.ws16;              // (the kernel writes raw slabs; bias, residual and y_act belong to the slab sum)
+    }
+    const RowP& p = pl.r;
+    pl.grid = rows_grid(bm, p);
+    // Does the launch go to the pipelined kernels (conv_rows2.hip, conv_rows3.hip)?  16-byte aligned operands, zero padding,
+    // plain input rows, activation handling they know; backward data additionally needs the forward-layout weights, which
+    // act_mode 1 reads directly.  Fills q, tile, am, in_s.
+    auto pipelined = [&](int K2, int CC2) {
+        pl.in_s = in_s;
+        if (p.pad_mode != MS_PAD_ZERO || cfg == ROW_64x256) return false;
+        if (has_act && p.in_act != MS_ACT_LRELU && p.in_act != MS_ACT_NONE && p.in_act != MS_MOD_LRELU_FWD) return false;
+        int am = (has_act && p.in_act == MS_ACT_LRELU) ? (in_s == 1 ? 1 : 2) : 0;
+        if (has_act && p.in_act == MS_MOD_LRELU_FWD) am = 3;      // LeakyReLU in front of the conv, on load
+        pl.am = am;
+        if (in_s != 1 && am != 2 && am != 0) return false;
+        if (am == 1 && (!wfwd || p.M % 4)) return false;
+        if (!(c.x16 && c.xact16 && out16 && ((am == 1 || !wbytes) ? c.w16 : c.ws16))) return false;
+        if ((long long)p.B * p.CK * p.L >= (1LL << 31) || (long long)p.M * p.KG >= (1LL << 31)) return false;
+        Row2P& q = pl.q;
+        q.B = p.B; q.CK = p.CK; q.L = p.L; q.M = p.M; q.dil = p.dil; q.off0 = p.off0; q.act = p.act;
+        q.KG = p.KG; q.Lt = p.Lt; q.R = p.R; q.SS = p.SS; q.RSZ = p.RSZ; q.tiles_per_row = p.tiles_per_row;
+        q.PX = p.RSZ; q.CKs = p.CKs; q.zstride = p.zstride; q.slope = p.slope; q.scratch_off = 0;
+        pl.tile = cfg == ROW_128x128 ? MSR2_128x128 : (cfg == ROW_64x128 ? MSR2_64x128 :
+                  (cfg == ROW_64x64 ? MSR2_64x64 : MSR2_32x256));
+        if (in_s == 1 && msr3_supported(pl.tile, K2, am, epi_s, q, 1)) return true;   // split-bf16 kernel: rows of any length
+        // short rows of a length that is not a multiple of 4 (k5 conv at L = 17 / 9): whole-row staging
+        if (in_s == 1 && K2 == 5 && p.tiles_per_row == 1 && p.Lt == p.L && p.L < bn && p.L % 4 != 0 &&
+            msr2_supported(pl.tile, K2, CC2, am, epi_s, q, 0)) {
+            pl.in_s = 0;
+            return true;
+        }
+        return msr3_supported(pl.tile, K2, am, epi_s, q, in_s) || msr2_supported(pl.tile, K2, CC2, am, epi_s, q, in_s);
+    };
+    if (conv_t && pipelined(2, 8)) {       // the 3-tap window stays, only the two live taps of each phase are multiplied
+        pl.fam = RowPlan::ROWS2; pl.K = 2; pl.CC = 8;
+        pl.q.KG = p.CK * 2;
+        if (pair_t) {                      // paired split-bf16 kernel where its grid fills the chip
+            if (const int b3 = rows3p_convt_bm(pl.q, bn, epi_s, pl.grid.z)) {
+                pl.fam = RowPlan::ROWS3P_T; pl.bmp = b3;
+                pl.grid = msr3p_grid(b3, pl.q, pl.grid.z);
+            }
+        }
+    } else if (pipelined(K, pl.CC)) {
+        int bmp = rows3p_bm(pl.q, bn, K, pl.am, epi_s, pl.in_s, pl.grid.z);
+        if (!bmp && cfg == ROW_32x256 && pl.q.R == 1 && pl.q.Lt == 256) {      // 32-channel layers: the same rows as 128-column tiles
+            const Row2P q2 = rows3p_retile(pl.q, K);
+            if ((bmp = rows3p_bm(q2, 128, K, pl.am, epi_s, pl.in_s, pl.grid.z)) != 0) pl.q = q2;
+        }
+        if (bmp) {
+            pl.fam = RowPlan::ROWS3P; pl.bmp = bmp;
+            pl.grid = msr3p_grid(bmp, pl.q, pl.grid.z);
+        } else {
+            // split-bf16 matrix pipe (conv_rows3.hip) before the fp32 one
+            pl.fam = msr3_supported(pl.tile, K, pl.am, epi_s, pl.q, pl.in_s) ? RowPlan::ROWS3 : RowPlan::ROWS2;
+        }
+    } else {
+        pl.am = 0; pl.in_s = in_s;
+    }
+    return pl;
+}
+
+struct RowOps {
+    const float *X, *Xact, *W, *Wfwd, *bias, *res;   // W: the layout the plan's pack kernel wrote (or the call's own); Wfwd: act_mode 1
+    float *Y, *Yact;
+};
+
+template <int K, int CC, bool HAS_ACT, int EPI_S, int IN_S>
+int launch_rows1_k(const RowPlan& pl, const RowOps& o, hipStream_t s, char* name) {
+    const RowP& p = pl.r;
+    int bm, bn;
+    row_tile(pl.cfg, &bm, &bn);
+    const size_t lds = (size_t)(bm * (CC * K + 1) + CC * p.RSZ) * sizeof(float);
+    if (lds > 64 * 1024) return MS_ERR_UNSUPPORTED;
+#define MS_R1(WGM, WGN, TM, TN)                                                                                         \
+    do {                                                                                                                \
+        if (ms_name_or_note(name, 0, "k_conv_mfma_rows<%d, %d, %d, %d, %d, %d, %s, %d, %d>", WGM, WGN, TM, TN, K, CC,     \
+                            HAS_ACT ? "true" : "false", EPI_S, IN_S))                                                   \
+            return MS_OK;                                                                                               \
+        hipLaunchKernelGGL((k_conv_mfma_rows<WGM, WGN, TM, TN, K, CC, HAS_ACT, EPI_S, IN_S>), pl.grid, dim3(256), lds, s, \
+                           p, o.X, o.Xact, o.W, o.bias, o.res, o.Y, o.Yact);                                            \
+    } while (0)
+    switch (pl.cfg) {
+        case ROW_128x128: MS_R1(2, 2, 2, 2); break;
+        case ROW_64x128: MS_R1(2, 2, 1, 2); break;
+        case ROW_64x64: MS_R1(2, 2, 1, 1); break;
+        case ROW_64x256: MS_R1(1, 4, 2, 2); break;
+        default: MS_R1(1, 4, 1, 2); break;
+    }
+#undef MS_R1
     MS_CHECK_LAUNCH();
     return MS_OK;
 }
 
-int rows_cc_eff(int K, int CK) { return row_cc(K) * (row_deep(K, CK) ? 2 : 1); }
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-bool rows_ok(const ConvP& p, bool bwd) {
-    const int M = bwd ? p.Cin : p.Cout, CK = bwd ? p.Cout : p.Cin;
-    if (!rows_applicable(M, CK, p.K, p.Lin)) return false;
-    if (((size_t)CK * p.K) % 4) return false;
-    RowP q;
-    return make_rowp(&q, pick_row_cfg(M, p.B, p.Lin), p.B, CK, p.Lin, M, p.K, p.dil, 0, 0, 0, 0, 0.f);
+// first-generation kernel of a plan: the instantiations that exist
+int launch_rows1(const RowPlan& pl, const RowOps& o, hipStream_t s, char* name) {
+    const int K = pl.K, CC = pl.CC;
+#define MS_R1K(KK, C, E, I)                                                               \
+    if (K == KK && CC == C && pl.epi_s == E && pl.in_s == I)                              \
+        return pl.has_act ? launch_rows1_k<KK, C, true, E, I>(pl, o, s, name)             \
+                          : launch_rows1_k<KK, C, false, E, I>(pl, o, s, name)
+    MS_R1K(1, 32, 0, 1);
+    MS_R1K(3, 8, 0, 1);
+    MS_R1K(3, 16, 0, 1);
+    MS_R1K(5, 8, 0, 1);
+    MS_R1K(5, 16, 0, 1);
+    MS_R1K(7, 4, 0, 1);
+    MS_R1K(3, 8, 8, 1);      // transposed-conv forward: phase-interleaving epilogue
+    MS_R1K(3, 8, 2, 1);
+#undef MS_R1K
+    if (K == 3 && CC == 8 && pl.epi_s == 0 && pl.has_act) {      // transposed-conv backward data: phase-split input rows
+        if (pl.in_s == 8) return launch_rows1_k<3, 8, true, 0, 8>(pl, o, s, name);
+        if (pl.in_s == 2) return launch_rows1_k<3, 8, true, 0, 2>(pl, o, s, name);
+    }
+    return MS_ERR_UNSUPPORTED;
 }
 
-const char* kname(const char* kernel, Cfg c, int K, const char* tail) {
-    static thread_local char buf[96];
-    const char* tile = c == CFG_128x128 ? "2, 2, 2, 2" : (c == CFG_64x64 ? "2, 2, 1, 1" :
-                       (c == CFG_32x128 ? "1, 4, 1, 1" : "1, 4, 1, 2"));
-    snprintf(buf, sizeof(buf), "%s<%s, %d%s>", kernel, tile, K, tail);
-    return buf;
+// Runs the row-tile launch of a plan, then the slab sum of a split one.  slabs: the workspace behind the re-laid-out weights.
+int run_rows(const RowPlan& pl, const RowOps& o, float* slabs, hipStream_t s, char* name) {
+    RowOps k = o;          // the kernel's operands: a split launch writes raw slabs, its epilogue belongs to the slab sum
+    if (pl.ns > 1) { k.bias = nullptr; k.res = nullptr; k.Y = slabs; k.Yact = nullptr; }
+    const float* W = pl.am == 1 ? o.Wfwd : o.W;
+    int rc;
+    switch (pl.fam) {
+        case RowPlan::ROWS3P:
+            rc = msr3p_launch(pl.bmp, pl.K, pl.am, pl.q, k.X, k.Xact, W, k.bias, k.res, k.Y, k.Yact, pl.grid, s, name);
+            break;
+        case RowPlan::ROWS3P_T:
+            rc = msr3p_convt_launch(pl.bmp, pl.epi_s, pl.am == 3, pl.q, k.X, W, k.bias, k.Y, pl.grid, s, name);
+            break;
+        case RowPlan::ROWS3:
+            rc = msr3_launch(pl.tile, pl.K, pl.am, pl.q, k.X, k.Xact, W, k.bias, k.res, k.Y, k.Yact, pl.grid, s, name);
+            break;
+        case RowPlan::ROWS2:
+            rc = msr2_launch(pl.tile, pl.K, pl.CC, pl.am, pl.epi_s, pl.q, k.X, k.Xact, W, k.bias, k.res, k.Y, k.Yact, pl.grid, s,
+                             pl.in_s, name);
+            break;
+        default: rc = launch_rows1(pl, k, s, name); break;
+    }
+    if (rc != MS_OK || name || pl.ns <= 1) return rc;
+    hipLaunchKernelGGL(k_rows_split_finish, blocks256(pl.out_floats, 2048), dim3(256), 0, s, slabs, pl.ns, pl.out_floats,
+                       o.bias, pl.nch, pl.rowlen, pl.act, pl.r.slope, o.res, o.Y, o.Yact, pl.out_floats);
+    MS_CHECK_LAUNCH();
+    return MS_OK;
 }
+
+// ---- the planners, one per pass
+// x_act_kind: operand-modifier kind of the activation operand (0: none rides along)
+RowPlan plan_fwd(const ConvP& p, bool has_act, int x_act_kind, const RowCall& c) {
+    if (rows_ok(p, false) && c.w16) {
+        RowP r;
+        const RowCfg cfg = pick_row_cfg(p.Cout, p.B, p.Lin, p.K == 3 || p.K == 5);
+        make_rowp(&r, cfg, p.B, p.Cin, p.Lin, p.Cout, p.K, p.dil, -p.pad, p.pad_mode, p.act, x_act_kind, p.slope);
+        return plan_rows(cfg, r, p.K, has_act, 0, 1, false, false, 0, false, p.Cout, p.Lin, c);
+    }
+    RowPlan pl;
+    pl.icfg = pick_cfg(p.Cout, (long long)p.B * p.Lin);
+    return pl;
+}
+
+// has_act: y_act rides along.  The row tiles need the whole workspace (re-laid-out weights | slabs) at a 16-byte address.
+RowPlan plan_bwd_data(const ConvP& p, bool has_act, const RowCall& c) {
+    if (rows_ok(p, true)) {
+        RowP r;
+        const RowCfg cfg = pick_row_cfg(p.Cin, p.B, p.Lin, p.K == 3 || p.K == 5);
+        make_rowp(&r, cfg, p.B, p.Cout, p.Lin, p.Cin, p.K, p.dil, p.pad - (p.K - 1) * p.dil, MS_PAD_ZERO, MS_ACT_NONE, p.act,
+                  p.slope);
+        RowPlan pl = plan_rows(cfg, r, p.K, has_act, 0, 1, false, false, align16((size_t)p.Cin * p.Cout * p.K * sizeof(float)),
+                               true, p.Cin, p.Lin, c);
+        // the pipelined kernels read the forward layout directly (act_mode 1); the others get it transposed + tap-flipped
+        pl.pack = pl.fam != RowPlan::ROWS1 && pl.am == 1 ? RowPlan::PACK_NONE : RowPlan::FLIP_W;
+        if (c.ws && c.ws16 && c.ws_bytes >= pl.bytes) return pl;
+    }
+    RowPlan pl;
+    pl.icfg = pick_cfg(p.Cin, (long long)p.B * p.Lin);
+    return pl;
+}
+
+// p = mirrored conv of the transposed conv: Cin_T = p.Cout, Cout_T = p.Cin, Lin_T = p.Lout.  The activation operand of the
+// forward is x itself (LeakyReLU in front, applied on load).
+RowPlan plan_convt_fwd(const ConvP& p, const RowCall& c) {
+    const int S = p.stride;
+    RowP r;
+    const RowCfg cfg = convt_fwd_cfg(p.Cin * S, p.B, p.Lout);
+    make_rowp(&r, cfg, p.B, p.Cout, p.Lout, p.Cin * S, 3, 1, -1, MS_PAD_ZERO, p.act, p.in_act ? MS_MOD_LRELU_FWD : MS_ACT_NONE,
+              p.slope);
+    RowPlan pl = plan_rows(cfg, r, 3, p.in_act != 0, S, 1, true, true, align16((size_t)p.Cin * S * p.Cout * 3 * sizeof(float)),
+                           false, p.Cin, p.Lout * S, c);
+    pl.pack = pl.K == 2 ? RowPlan::PACK_T2 : RowPlan::PACK_T;
+    return pl;
+}
+
+// gx_T = conv over the phase-split gradient: M = Cin_T, channels (co, r), 3 taps.  has_act: y_act rides along (else the
+// activation operand aliases the data, pass-through kind)
+RowPlan plan_convt_bwd_data(const ConvP& p, bool has_act, const RowCall& c) {
+    const int S = p.stride;
+    RowP r;
+    const RowCfg cfg = pick_row_cfg(p.Cout, p.B, p.Lout);
+    make_rowp(&r, cfg, p.B, p.Cin * S, p.Lout, p.Cout, 3, 1, -1, MS_PAD_ZERO, MS_ACT_NONE, has_act ? p.act : MS_ACT_NONE, p.slope);
+    RowPlan pl = plan_rows(cfg, r, 3, true, 0, S, true, false, align16((size_t)p.Cout * p.Cin * S * 3 * sizeof(float)), false,
+                           p.Cout, p.Lout, c);
+    pl.pack = pl.K == 2 ? RowPlan::PACK_TB2 : RowPlan::PACK_TB;
+    return pl;
+}
+
+// runs a forward / backward-data plan that fell to the im2col kernel
+template <bool TRANS>
+int run_igemm(const RowPlan& pl, const ConvP& p, int in_act, const RowOps& o, hipStream_t s, char* name) {
+    IgP q;
+    q.B = p.B; q.CK = TRANS ? p.Cout : p.Cin; q.L = p.Lin; q.M = TRANS ? p.Cin : p.Cout; q.dil = p.dil;
+    q.off0 = TRANS ? p.pad - (p.K - 1) * p.dil : -p.pad;   // backward data: flipped taps, j' = K-1-j
+    q.pad_mode = TRANS ? (int)MS_PAD_ZERO : p.pad_mode; q.act = TRANS ? (int)MS_ACT_NONE : p.act; q.in_act = in_act;
+    q.slope = p.slope; q.N = p.B * p.Lin; q.KG = q.CK * p.K; q.in_s = 1;
+    return launch_conv<TRANS>(p.K, pl.icfg, q, o.X, o.Xact, o.W, o.bias, o.res, o.Y, o.Yact, s, name);
+}
+
+int run_fwd(const RowPlan& pl, const ConvP& p, int x_act_kind, const RowOps& o, void* ws, hipStream_t s, char* name) {
+    if (pl.fam == RowPlan::IGEMM) return run_igemm<false>(pl, p, x_act_kind, o, s, name);
+    return run_rows(pl, o, (float*)ws, s, name);
+}
+
+int run_bwd_data(const RowPlan& pl, const ConvP& p, RowOps o, void* ws, hipStream_t s, char* name) {
+    if (pl.fam == RowPlan::IGEMM) return run_igemm<true>(pl, p, p.act, o, s, name);
+    float* wt = (float*)ws;
+    if (pl.pack == RowPlan::FLIP_W && !name) {
+        hipLaunchKernelGGL(k_transpose_flip_w, blocks256((size_t)p.Cin * p.Cout * p.K, 2048), dim3(256), 0, s, o.Wfwd, wt, p.Cout,
+                           p.Cin, p.K);
+        MS_CHECK_LAUNCH();
+    }
+    o.W = wt;
+    return run_rows(pl, o, (float*)((char*)ws + pl.wbytes), s, name);
+}
+
+// both transposed passes: the plan's pack kernel writes the phase-split weights to the front of the workspace
+int run_convt(const RowPlan& pl, const ConvP& p, RowOps o, const float* w, void* ws, hipStream_t s, char* name) {
+    float* wp = (float*)ws;
+    if (!name) {
+        const int S = p.stride, CinT = p.Cout, CoutT = p.Cin;
+        const dim3 nb = blocks256((size_t)CinT * CoutT * S * 3, 4096);
+        if (pl.pack == RowPlan::PACK_T2) hipLaunchKernelGGL(k_pack_convt_w2, nb, dim3(256), 0, s, w, wp, CinT, CoutT, p.K, S, p.pad);
+        else if (pl.pack == RowPlan::PACK_T) hipLaunchKernelGGL(k_pack_convt_w, nb, dim3(256), 0, s, w, wp, CinT, CoutT, p.K, S, p.pad);
+        else if (pl.pack == RowPlan::PACK_TB2) hipLaunchKernelGGL(k_pack_convt_bwd_w2, nb, dim3(256), 0, s, w, wp, CinT, CoutT, p.K, S, p.pad);
+        else hipLaunchKernelGGL(k_pack_convt_bwd_w, nb, dim3(256), 0, s, w, wp, CinT, CoutT, p.K, S, p.pad);
+        MS_CHECK_LAUNCH();
+    }
+    o.W = wp;
+    return run_rows(pl, o, (float*)((char*)ws + pl.wbytes), s, name);
+}
+
+IgP wgrad_igp(const ConvP& p) {
+    IgP q;
+    q.B = p.B; q.CK = p.Cin; q.L = p.Lin; q.M = p.Cout; q.dil = p.dil; q.off0 = -p.pad;
+    q.pad_mode = p.pad_mode; q.act = MS_ACT_NONE; q.in_act = 0; q.slope = p.slope;
+    q.N = p.B * p.Lin; q.KG = p.Cin * p.K; q.in_s = 1;
+    return q;
+}
+
+bool wgrad_v4(const ConvP& p, bool aligned) { return p.Lin % 4 == 0 && p.pad_mode == MS_PAD_ZERO && aligned; }
+
+struct ConvtWgradPlan {
+    WgradPlan w;
+    IgP q;
+    size_t dwq_floats;
+};
+
+ConvtWgradPlan plan_convt_wgrad(const ConvP& p) {
+    // weight-grad GEMM: M = Cin_T, N = Cout_T * S * 3, K = B * Lin_T
+    ConvP m = p;
+    m.Cout = p.Cout;                 // rows: x_T channels
+    m.Cin = p.Cin * p.stride;        // (co, r) phase channels
+    m.K = 3; m.Lin = p.Lout; m.Lout = p.Lout; m.stride = 1; m.pad = 1; m.dil = 1;
+    m.pad_mode = MS_PAD_ZERO;
+    ConvtWgradPlan q;
+    q.w = plan_wgrad(m);
+    q.q = wgrad_igp(m);
+    q.q.in_act = p.act; q.q.in_s = p.stride;
+    q.dwq_floats = (size_t)p.Cout * m.Cin * 3 + p.Cout;
+    return q;
+}
+
+// what a name query hands out: the spelling its plan's launcher wrote, in a buffer of the calling thread
+const char* named(int rc, const char* buf) { return rc == MS_OK ? buf : ""; }
 
 }  // namespace
 
@@ -1460,151 +1645,47 @@ bool msm_convt_fwd_applicable(const ConvP& p) {
     RowP q;
     return make_rowp(&q, convt_fwd_cfg(p.Cin * S, p.B, p.Lout), p.B, p.Cout, p.Lout, p.Cin * S, 3, 1, -1, 0, 0, 0, 0.f);
 }
-size_t msm_fwd_ws(const ConvP& p) {
-    if (!rows_ok(p, false)) return 0;
-    RowP r;
-    const RowCfg cfg = pick_row_cfg(p.Cout, p.B, p.Lin, p.K == 3 || p.K == 5);
-    make_rowp(&r, cfg, p.B, p.Cin, p.Lin, p.Cout, p.K, p.dil, -p.pad, p.pad_mode, 0, 0, 0.f);
-    return rows_split_ws(cfg, r, rows_cc_eff(p.K, p.Cin));
-}
-size_t msm_bwd_data_ws(const ConvP& p) {
-    if (!rows_ok(p, true)) return 0;
-    RowP r;
-    const RowCfg cfg = pick_row_cfg(p.Cin, p.B, p.Lin, p.K == 3 || p.K == 5);
-    make_rowp(&r, cfg, p.B, p.Cout, p.Lin, p.Cin, p.K, p.dil, 0, 0, 0, 0, 0.f);
-    return align16((size_t)p.Cin * p.Cout * p.K * sizeof(float)) + rows_split_ws(cfg, r, rows_cc_eff(p.K, p.Cout));
-}
+
+// ---- the queries: the plan of a call with 16-byte aligned operands and the queried workspace; a forward's activation operand
+// is the descriptor's in_act, a backward pass has y_act where the layer has an activation
+size_t msm_fwd_ws(const ConvP& p) { return plan_fwd(p, p.in_act != 0, p.in_act ? MS_MOD_LRELU_FWD : 0, RowCall()).bytes; }
+size_t msm_bwd_data_ws(const ConvP& p) { return plan_bwd_data(p, p.act != MS_ACT_NONE, RowCall()).bytes; }
 size_t msm_bwd_weight_ws(const ConvP& p) {
     const WgradPlan q = plan_wgrad(p);
     return (size_t)q.nsplit * q.stride_floats * sizeof(float);
 }
-size_t msm_convt_fwd_ws(const ConvP& p) {
-    RowP r;
-    const RowCfg cfg = convt_fwd_cfg(p.Cin * p.stride, p.B, p.Lout);
-    make_rowp(&r, cfg, p.B, p.Cout, p.Lout, p.Cin * p.stride, 3, 1, -1, 0, 0, 0, 0.f);
-    return align16((size_t)p.Cin * p.stride * p.Cout * 3 * sizeof(float)) + rows_split_ws(cfg, r, row_cc(3));
-}
+size_t msm_convt_fwd_ws(const ConvP& p) { return plan_convt_fwd(p, RowCall()).bytes; }
 
-const char* msm_fwd_name(const ConvP& p) {
-    if (rows_ok(p, false)) {
-        RowP r;
-        const RowCfg cfg = pick_row_cfg(p.Cout, p.B, p.Lin, p.K == 3 || p.K == 5);
-        make_rowp(&r, cfg, p.B, p.Cin, p.Lin, p.Cout, p.K, p.dil, -p.pad, p.pad_mode, 0, 0, 0.f);
-        return row_kname(cfg, p.K, p.in_act != 0, p.Cin, p.Lin, r.R, r.SS, p.pad_mode, p.in_act ? MS_MOD_LRELU_FWD : 0, 0,
-                         p.B, p.Cout);
-    }
-    return kname("k_igemm_conv", pick_cfg(p.Cout, (long long)p.B * p.Lin), p.K, ", false");
+const char* msm_fwd_name(const ConvP& p, int x_act_kind) {
+    static thread_local char buf[MS_PROFILE_NAME_MAX];
+    return named(run_fwd(plan_fwd(p, x_act_kind != 0, x_act_kind, RowCall()), p, x_act_kind, RowOps(), nullptr, nullptr, buf), buf);
 }
+const char* msm_fwd_name(const ConvP& p) { return msm_fwd_name(p, p.in_act ? MS_MOD_LRELU_FWD : 0); }
 const char* msm_bwd_data_name(const ConvP& p) {
-    if (rows_ok(p, true)) {
-        RowP r;
-        const RowCfg cfg = pick_row_cfg(p.Cin, p.B, p.Lin, p.K == 3 || p.K == 5);
-        make_rowp(&r, cfg, p.B, p.Cout, p.Lin, p.Cin, p.K, p.dil, 0, 0, 0, 0, 0.f);
-        return row_kname(cfg, p.K, p.act != MS_ACT_NONE, p.Cout, p.Lin, r.R, r.SS, MS_PAD_ZERO, p.act, 0, p.B, p.Cin);
-    }
-    return kname("k_igemm_conv", pick_cfg(p.Cin, (long long)p.B * p.Lin), p.K, ", true");
+    static thread_local char buf[MS_PROFILE_NAME_MAX];
+    return named(run_bwd_data(plan_bwd_data(p, p.act != MS_ACT_NONE, RowCall()), p, RowOps(), nullptr, nullptr, buf), buf);
 }
 const char* msm_bwd_weight_name(const ConvP& p) {
-    const bool v4 = (p.Lin % 4 == 0) && p.pad_mode == MS_PAD_ZERO;
-    return kname(v4 ? "k_igemm_wgrad_v4" : "k_igemm_wgrad", plan_wgrad(p).cfg, p.K, "");
+    static thread_local char buf[MS_PROFILE_NAME_MAX];
+    return named(launch_wgrad(plan_wgrad(p), p.K, wgrad_v4(p, true), wgrad_igp(p), nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                              nullptr, buf), buf);
 }
 const char* msm_convt_fwd_name(const ConvP& p) {
-    static thread_local char buf[96];
-    const RowCfg c = convt_fwd_cfg(p.Cin * p.stride, p.B, p.Lout);
-    RowP r;
-    make_rowp(&r, c, p.B, p.Cout, p.Lout, p.Cin * p.stride, 3, 1, -1, 0, 0, 0, 0.f);
-    {   // the paired split-bf16 kernel, decided exactly as msm_convt1d_fwd does (dummy 16-byte aligned pointers)
-        RowP r2 = r;
-        if (p.in_act) r2.in_act = MS_MOD_LRELU_FWD;
-        const float* D = reinterpret_cast<const float*>(uintptr_t(64));
-        Row2P q;
-        int tile = 0, am = 0, bm = 0, bn = 0;
-        if (rows2_pick(c, 2, 8, p.in_act != 0, p.stride, 1, r2, D, p.in_act ? D : nullptr, D, nullptr, D, nullptr, &q, &tile, &am)) {
-            q.KG = r.CK * 2;
-            const RowSplit sp = plan_rows_split(c, r, row_cc(3));
-            if (sp.ns > 1) q.CKs = sp.cks;
-            const unsigned gz = (unsigned)((q.CK + q.CKs - 1) / q.CKs);
-            row_tile(c, &bm, &bn);
-            int b3 = rows3p_convt_bm(q, bn, p.stride, gz);
-            if (!b3 && c == ROW_32x256 && q.R == 1 && q.Lt == 256) b3 = rows3p_convt_bm(rows3p_retile(q, 3), 128, p.stride, gz);
-            if (b3) {
-                snprintf(buf, sizeof(buf), "k_conv_rows3p<2, %d, 2, 3, 0, %d, %s>", b3 == 128 ? 2 : 1, p.stride,
-                         p.in_act ? "true" : "false");
-                return buf;
-            }
-        }
-    }
-    if (c == ROW_128x128 || c == ROW_64x128) {
-        Row2P q;
-        q.L = p.Lout; q.R = r.R; q.SS = r.SS; q.M = p.Cin * p.stride;
-        const int am = p.in_act ? 3 : 0;
-        if (msr2_supported(c == ROW_128x128 ? MSR2_128x128 : MSR2_64x128, 2, 8, am, p.stride, q)) {
-            snprintf(buf, sizeof(buf), "k_conv_rows2<%s, 2, 8, %d, %d>", c == ROW_128x128 ? "2, 2, 2, 2" : "1, 4, 2, 1", am, p.stride);
-            return buf;
-        }
-    }
-    return row_kname(c, 3, p.in_act != 0, p.Cout, p.Lout, r.R, r.SS, MS_PAD_ZERO, p.in_act ? MS_MOD_LRELU_FWD : 0, p.stride);
+    static thread_local char buf[MS_PROFILE_NAME_MAX];
+    return named(run_convt(plan_convt_fwd(p, RowCall()), p, RowOps(), nullptr, nullptr, nullptr, buf), buf);
 }
 
 int msm_conv1d_fwd(const ConvP& p, const float* x, const float* x_act, int x_act_kind,
                    const float* w, const float* bias, const float* residual, float* y,
                    float* y_act, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (rows_ok(p, false) && (((uintptr_t)w) & 15) == 0) {
-        RowP r;
-        const RowCfg cfg = pick_row_cfg(p.Cout, p.B, p.Lin, p.K == 3 || p.K == 5);
-        make_rowp(&r, cfg, p.B, p.Cin, p.Lin, p.Cout, p.K, p.dil, -p.pad, p.pad_mode, p.act,
-                  x_act_kind, p.slope);
-        const int K = p.K;
-        return rows_maybe_split(cfg, r, rows_cc_eff(K, p.Cin), p.Cout, p.Lin, bias, residual, y, y_act,
-                                ws, ws_bytes, s,
-                                [&](const RowP& rp, const float* b_, const float* r_, float* y_, float* ya_) {
-                                    return launch_rows(K, cfg, rp, x, x_act, w, b_, r_, y_, ya_, s);
-                                });
-    }
-    IgP q;
-    q.B = p.B; q.CK = p.Cin; q.L = p.Lin; q.M = p.Cout; q.dil = p.dil; q.off0 = -p.pad;
-    q.pad_mode = p.pad_mode; q.act = p.act; q.in_act = x_act_kind; q.slope = p.slope;
-    q.N = p.B * p.Lin; q.KG = p.Cin * p.K; q.in_s = 1;
-    return launch_conv<false>(p.K, pick_cfg(q.M, q.N), q, x, x_act, w, bias, residual, y, y_act, s);
+    const RowPlan pl = plan_fwd(p, x_act != nullptr, x_act_kind, row_call(x, x_act, w, residual, y, y_act, ws, ws_bytes));
+    return run_fwd(pl, p, x_act_kind, RowOps{x, x_act, w, nullptr, bias, residual, y, y_act}, ws, s, nullptr);
 }
 
 int msm_conv1d_bwd_data(const ConvP& p, const float* gy, const float* y_act, const float* w,
                         const float* gx_add, float* gx, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (rows_ok(p, true) && ws && ws_bytes >= msm_bwd_data_ws(p) && (((uintptr_t)ws) & 15) == 0) {
-        float* wt = (float*)ws;
-        const size_t total = (size_t)p.Cin * p.Cout * p.K;
-        const size_t wbytes = align16(total * sizeof(float));
-        RowP r;
-        const RowCfg cfg = pick_row_cfg(p.Cin, p.B, p.Lin, p.K == 3 || p.K == 5);
-        make_rowp(&r, cfg, p.B, p.Cout, p.Lin, p.Cin, p.K, p.dil, p.pad - (p.K - 1) * p.dil,
-                  MS_PAD_ZERO, MS_ACT_NONE, p.act, p.slope);
-        r.Wfwd = w;
-        {
-            Row2P q2;
-            int tile2, am2;
-            int ins2;
-            const bool direct = y_act && rows2_pick(cfg, p.K, rows_cc_eff(p.K, p.Cout), true, 0, 1, r, gy, y_act, wt,
-                                                    gx_add, gx, nullptr, &q2, &tile2, &am2, &ins2) && am2 == 1;
-            if (!direct) {     // first-generation kernel: weights re-laid-out (transposed + tap-flipped)
-                unsigned nb = (unsigned)((total + 255) / 256);
-                if (nb > 2048) nb = 2048;
-                hipLaunchKernelGGL(k_transpose_flip_w, dim3(nb), dim3(256), 0, s, w, wt, p.Cout, p.Cin, p.K);
-                MS_CHECK_LAUNCH();
-            }
-        }
-        const int K = p.K;
-        return rows_maybe_split(cfg, r, rows_cc_eff(K, p.Cout), p.Cin, p.Lin, nullptr, gx_add, gx, nullptr,
-                                (char*)ws + wbytes, ws_bytes - wbytes, s,
-                                [&](const RowP& rp, const float* b_, const float* r_, float* y_, float* ya_) {
-                                    return launch_rows(K, cfg, rp, gy, y_act, wt, b_, r_, y_, ya_, s);
-                                });
-    }
-    IgP q;
-    q.B = p.B; q.CK = p.Cout; q.L = p.Lin; q.M = p.Cin; q.dil = p.dil;
-    q.off0 = p.pad - (p.K - 1) * p.dil;   // flipped taps: j' = K-1-j
-    q.pad_mode = MS_PAD_ZERO; q.act = MS_ACT_NONE; q.in_act = p.act; q.slope = p.slope;
-    q.N = p.B * p.Lin; q.KG = p.Cout * p.K; q.in_s = 1;
-    return launch_conv<true>(p.K, pick_cfg(q.M, q.N), q, gy, y_act, w, nullptr, gx_add, gx, nullptr, s);
+    const RowPlan pl = plan_bwd_data(p, y_act != nullptr, row_call(gy, y_act, w, gx_add, gx, nullptr, ws, ws_bytes));
+    return run_bwd_data(pl, p, RowOps{gy, y_act, w, w, nullptr, gx_add, gx, nullptr}, ws, s, nullptr);
 }
 
 int msm_conv1d_bwd_weight(const ConvP& p, const float* x, const float* x_act, int x_act_kind,
@@ -1613,100 +1694,22 @@ int msm_conv1d_bwd_weight(const ConvP& p, const float* x, const float* x_act, in
     const WgradPlan pl = plan_wgrad(p);
     const size_t need = (size_t)pl.nsplit * pl.stride_floats * sizeof(float);
     if (!ws || ws_bytes < need) return MS_ERR_WORKSPACE;
-    IgP q;
-    q.B = p.B; q.CK = p.Cin; q.L = p.Lin; q.M = p.Cout; q.dil = p.dil; q.off0 = -p.pad;
-    q.pad_mode = p.pad_mode; q.act = MS_ACT_NONE; q.in_act = x_act_kind; q.slope = p.slope;
-    q.N = p.B * p.Lin; q.KG = p.Cin * p.K; q.in_s = 1;
-    const int NG = p.Cin * p.K;
-    dim3 grid((unsigned)ms_ceil_div(NG, pl.bn), (unsigned)ms_ceil_div(p.Cout, pl.bm), (unsigned)pl.nsplit);
+    IgP q = wgrad_igp(p);
+    q.in_act = x_act_kind;
     float* partial = (float*)ws;
-    const bool v4 = (p.Lin % 4 == 0) && p.pad_mode == MS_PAD_ZERO &&
-                    ((((uintptr_t)x) | ((uintptr_t)gy) | ((uintptr_t)(y_act ? y_act : gy))) & 15) == 0;
-#define MS_WG(WGM, WGN, TM, TN, KK)                                                                 \
-    do {                                                                                            \
-        if (v4)                                                                                     \
-            hipLaunchKernelGGL((k_igemm_wgrad_v4<WGM, WGN, TM, TN, KK>), grid, dim3(256), 0, s, q,  \
-                               pl.cps, x, x_act, gy, y_act, y_act_kind, partial, pl.stride_floats); \
-        else                                                                                        \
-            hipLaunchKernelGGL((k_igemm_wgrad<WGM, WGN, TM, TN, KK>), grid, dim3(256), 0, s, q,     \
-                               pl.cps, x, x_act, gy, y_act, y_act_kind, partial, pl.stride_floats); \
-    } while (0)
-#define MS_WG_K(KK)                                                                                 \
-    do {                                                                                            \
-        if (pl.cfg == CFG_128x128) MS_WG(2, 2, 2, 2, KK);                                           \
-        else if (pl.cfg == CFG_64x64) MS_WG(2, 2, 1, 1, KK);                                        \
-        else if (pl.cfg == CFG_32x128) MS_WG(1, 4, 1, 1, KK);                                       \
-        else MS_WG(1, 4, 1, 2, KK);                                                                 \
-    } while (0)
-    if (p.K == 1) MS_WG_K(1);
-    else if (p.K == 3) MS_WG_K(3);
-    else if (p.K == 5) MS_WG_K(5);
-    else if (p.K == 7) MS_WG_K(7);
-    else if (p.K == 15) MS_WG_K(15);
-    else return MS_ERR_UNSUPPORTED;
-#undef MS_WG_K
-#undef MS_WG
-    MS_CHECK_LAUNCH();
-    return msm_wgrad_reduce(partial, pl.stride_floats, pl.nsplit, (size_t)p.Cout * NG, p.Cout, gw, gb, beta, s);
+    const int rc = launch_wgrad(pl, p.K, wgrad_v4(p, al16(x) && al16(gy) && al16(y_act)), q, x, x_act, gy, y_act, y_act_kind,
+                                partial, s, nullptr);
+    if (rc != MS_OK) return rc;
+    return msm_wgrad_reduce(partial, pl.stride_floats, pl.nsplit, (size_t)p.Cout * q.KG, p.Cout, gw, gb, beta, s);
 }
 
 int msm_convt1d_fwd(const ConvP& p, const float* x, const float* w, const float* bias, float* y,
                     void* ws, size_t ws_bytes, hipStream_t s) {
-    const int S = p.stride, CinT = p.Cout, CoutT = p.Cin, LinT = p.Lout;
-    if (((uintptr_t)y) & 15) return MS_ERR_UNSUPPORTED;      // (phase-interleaved epilogue: 8- / 16-byte stores to y)
-    if (!ws || ws_bytes < msm_convt_fwd_ws(p) || (((uintptr_t)ws) & 15)) return MS_ERR_WORKSPACE;
-    float* wp = (float*)ws;
-    const size_t total = (size_t)CoutT * S * CinT * 3;
-    unsigned nb = (unsigned)((total + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    RowP r;
-    const RowCfg cfg = convt_fwd_cfg(CoutT * S, p.B, LinT);
-    make_rowp(&r, cfg, p.B, CinT, LinT, CoutT * S, 3, 1, -1, MS_PAD_ZERO, p.act, MS_ACT_NONE, p.slope);
-    const size_t wbytes = align16(total * sizeof(float));
-    const bool ia = p.in_act != 0;   // LeakyReLU in front of the transposed conv: applied to x on load
-    if (ia) r.in_act = MS_MOD_LRELU_FWD;
-    // pipelined kernel: the 3-tap window stays, but only the two live taps of each phase are multiplied
-    Row2P q2;
-    int tile2 = 0, am2 = 0;
-    const bool two = rows2_pick(cfg, 2, 8, ia, S, 1, r, x, ia ? x : nullptr, wp, nullptr, y, nullptr, &q2, &tile2, &am2);
-    if (two)
-        hipLaunchKernelGGL(k_pack_convt_w2, dim3(nb), dim3(256), 0, s, w, wp, CinT, CoutT, p.K, S, p.pad);
-    else
-        hipLaunchKernelGGL(k_pack_convt_w, dim3(nb), dim3(256), 0, s, w, wp, CinT, CoutT, p.K, S, p.pad);
-    MS_CHECK_LAUNCH();
-    return rows_maybe_split(cfg, r, row_cc(3), CoutT, LinT * S, bias, nullptr, y, nullptr,
-                            (char*)ws + wbytes, ws_bytes - wbytes, s,
-                            [&](const RowP& rp, const float* b_, const float* r_, float* y_, float* ya_) {
-                                if (two) {
-                                    Row2P q;
-                                    int tile, am, bm, bn;
-                                    if (!rows2_pick(cfg, 2, 8, ia, S, 1, rp, x, ia ? x : nullptr, wp, r_, y_, ya_, &q, &tile, &am))
-                                        return (int)MS_ERR_UNSUPPORTED;
-                                    q.KG = rp.CK * 2;
-                                    row_tile(cfg, &bm, &bn);
-                                    const unsigned gz_ = (unsigned)((rp.CK + rp.CKs - 1) / rp.CKs);
-                                    if (!r_ && !ya_) {     // paired split-bf16 kernel where its grid fills the chip
-                                        if (const int b3 = rows3p_convt_bm(q, bn, S, gz_))
-                                            return msr3p_convt_launch(b3, S, ia, q, x, wp, b_, y_, gz_, s);
-                                        if (cfg == ROW_32x256 && q.R == 1 && q.Lt == 256) {
-                                            Row2P q3 = rows3p_retile(q, 3);
-                                            if (const int b3 = rows3p_convt_bm(q3, 128, S, gz_))
-                                                return msr3p_convt_launch(b3, S, ia, q3, x, wp, b_, y_, gz_, s);
-                                        }
-                                    }
-                                    const unsigned gx_ = rp.R == 1 ? (unsigned)(rp.B * rp.tiles_per_row)
-                                                                   : (unsigned)((rp.B + rp.R - 1) / rp.R);
-                                    return msr2_launch(tile, 2, 8, am, S, q, x, nullptr, wp, b_, r_, y_, ya_, gx_,
-                                                       (unsigned)((rp.M + bm - 1) / bm),
-                                                       (unsigned)((rp.CK + rp.CKs - 1) / rp.CKs), s, 1);
-                                }
-                                if (ia) {
-                                    if (S == 8) return launch_rows_k<3, true, 8>(cfg, rp, x, x, wp, b_, r_, y_, ya_, s);
-                                    return launch_rows_k<3, true, 2>(cfg, rp, x, x, wp, b_, r_, y_, ya_, s);
-                                }
-                                if (S == 8) return launch_rows_k<3, false, 8>(cfg, rp, x, nullptr, wp, b_, r_, y_, ya_, s);
-                                return launch_rows_k<3, false, 2>(cfg, rp, x, nullptr, wp, b_, r_, y_, ya_, s);
-                            });
+    if (!al16(y)) return MS_ERR_UNSUPPORTED;      // (phase-interleaved epilogue: 8- / 16-byte stores to y)
+    const float* xa = p.in_act ? x : nullptr;     // LeakyReLU in front of the transposed conv: applied to x on load
+    const RowPlan pl = plan_convt_fwd(p, row_call(x, xa, w, nullptr, y, nullptr, ws, ws_bytes));
+    if (!ws || ws_bytes < pl.bytes || !al16(ws)) return MS_ERR_WORKSPACE;
+    return run_convt(pl, p, RowOps{x, xa, nullptr, nullptr, bias, nullptr, y, nullptr}, w, ws, s, nullptr);
 }
 
 // ---- ConvTranspose1d backward (p = mirrored conv: Cin_T = p.Cout, Cout_T = p.Cin, Lin_T = p.Lout)
@@ -1719,90 +1722,19 @@ bool msm_convt_bwd_applicable(const ConvP& p) {
     return make_rowp(&q, pick_row_cfg(p.Cout, p.B, p.Lout), p.B, p.Cin * S, p.Lout, p.Cout, 3, 1, -1, 0, 0, 0, 0.f);
 }
 
-size_t msm_convt_bwd_data_ws(const ConvP& p) {
-    RowP r;
-    const RowCfg cfg = pick_row_cfg(p.Cout, p.B, p.Lout);
-    make_rowp(&r, cfg, p.B, p.Cin * p.stride, p.Lout, p.Cout, 3, 1, -1, 0, 0, 0, 0.f);
-    return align16((size_t)p.Cout * p.Cin * p.stride * 3 * sizeof(float)) + rows_split_ws(cfg, r, row_cc(3));
-}
+size_t msm_convt_bwd_data_ws(const ConvP& p) { return plan_convt_bwd_data(p, p.act != MS_ACT_NONE, RowCall()).bytes; }
 
 const char* msm_convt_bwd_data_name(const ConvP& p) {
-    static thread_local char buf[96];
-    const RowCfg c = pick_row_cfg(p.Cout, p.B, p.Lout);
-    const char* tile = row_tile_str(c);
-    RowP r;
-    make_rowp(&r, c, p.B, p.Cin * p.stride, p.Lout, p.Cout, 3, 1, -1, 0, 0, 0, 0.f);
-    Row2P q;
-    q.L = p.Lout; q.R = r.R; q.SS = r.SS;
-    const int t2 = c == ROW_128x128 ? MSR2_128x128 : (c == ROW_64x128 ? MSR2_64x128 : (c == ROW_64x64 ? MSR2_64x64 : MSR2_32x256));
-    if (c != ROW_64x256 && p.act == MS_ACT_LRELU && msr2_supported(t2, 2, 8, 2, 0, q, p.stride))
-        snprintf(buf, sizeof(buf), "k_conv_rows2<%s, 2, 8, 2, 0, %d>", tile, p.stride);
-    else
-        snprintf(buf, sizeof(buf), "k_conv_mfma_rows<%s, 3, 8, true, 0, %d>", tile, p.stride);
-    return buf;
+    static thread_local char buf[MS_PROFILE_NAME_MAX];
+    return named(run_convt(plan_convt_bwd_data(p, p.act != MS_ACT_NONE, RowCall()), p, RowOps(), nullptr, nullptr, nullptr, buf), buf);
 }
 
-// gx_T = conv over the phase-split gradient: M = Cin_T, channels (co, r), 3 taps
 int msm_convt1d_bwd_data(const ConvP& p, const float* gy, const float* y_act, const float* w,
                          float* gx, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int S = p.stride, CinT = p.Cout, CoutT = p.Cin, LinT = p.Lout;
-    if (!ws || ws_bytes < msm_convt_bwd_data_ws(p) || (((uintptr_t)ws) & 15)) return MS_ERR_WORKSPACE;
-    float* wq = (float*)ws;
-    const size_t total = (size_t)CinT * CoutT * S * 3;
-    unsigned nb = (unsigned)((total + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    RowP r;
-    const RowCfg cfg = pick_row_cfg(CinT, p.B, LinT);
-    make_rowp(&r, cfg, p.B, CoutT * S, LinT, CinT, 3, 1, -1, MS_PAD_ZERO, MS_ACT_NONE, p.act, p.slope);
-    // the activation operand aliases the data when absent (pass-through kind)
     const float* ya = y_act ? y_act : gy;
-    if (!y_act) r.in_act = MS_ACT_NONE;
-    const size_t wbytes = align16(total * sizeof(float));
-    // pipelined kernel: the 3-tap window stays, but only the two live taps of each phase are multiplied
-    Row2P q2;
-    int tile2 = 0, am2 = 0;
-    const bool two = rows2_pick(cfg, 2, 8, true, 0, S, r, gy, ya, wq, nullptr, gx, nullptr, &q2, &tile2, &am2);
-    if (two)
-        hipLaunchKernelGGL(k_pack_convt_bwd_w2, dim3(nb), dim3(256), 0, s, w, wq, CinT, CoutT, p.K, S, p.pad);
-    else
-        hipLaunchKernelGGL(k_pack_convt_bwd_w, dim3(nb), dim3(256), 0, s, w, wq, CinT, CoutT, p.K, S, p.pad);
-    MS_CHECK_LAUNCH();
-    return rows_maybe_split(cfg, r, row_cc(3), CinT, LinT, nullptr, nullptr, gx, nullptr,
-                            (char*)ws + wbytes, ws_bytes - wbytes, s,
-                            [&](const RowP& rp, const float* b_, const float* r_, float* y_, float* ya_) {
-                                if (two) {
-                                    Row2P q;
-                                    int tile, am, bm, bn;
-                                    if (!rows2_pick(cfg, 2, 8, true, 0, S, rp, gy, ya, wq, r_, y_, ya_, &q, &tile, &am))
-                                        return (int)MS_ERR_UNSUPPORTED;
-                                    q.KG = rp.CK * 2;
-                                    row_tile(cfg, &bm, &bn);
-                                    const unsigned gx_ = rp.R == 1 ? (unsigned)(rp.B * rp.tiles_per_row)
-                                                                   : (unsigned)((rp.B + rp.R - 1) / rp.R);
-                                    return msr2_launch(tile, 2, 8, am, 0, q, gy, ya, wq, b_, r_, y_, ya_, gx_,
-                                                       (unsigned)((rp.M + bm - 1) / bm),
-                                                       (unsigned)((rp.CK + rp.CKs - 1) / rp.CKs), s, S);
-                                }
-                                if (S == 8) return launch_rows_k<3, true, 0, 8>(cfg, rp, gy, ya, wq, b_, r_, y_, ya_, s);
-                                return launch_rows_k<3, true, 0, 2>(cfg, rp, gy, ya, wq, b_, r_, y_, ya_, s);
-                            });
-}
-
-struct ConvtWgradPlan {
-    WgradPlan w;
-    size_t dwq_floats;
-};
-
-static ConvtWgradPlan plan_convt_wgrad(const ConvP& p) {
-    // weight-grad GEMM: M = Cin_T, N = Cout_T * S * 3, K = B * Lin_T
-    ConvP m = p;
-    m.Cout = p.Cout;                 // rows: x_T channels
-    m.Cin = p.Cin * p.stride;        // (co, r) phase channels
-    m.K = 3; m.Lin = p.Lout; m.Lout = p.Lout; m.stride = 1; m.pad = 1; m.dil = 1;
-    ConvtWgradPlan q;
-    q.w = plan_wgrad(m);
-    q.dwq_floats = (size_t)p.Cout * m.Cin * 3 + p.Cout;
-    return q;
+    const RowPlan pl = plan_convt_bwd_data(p, y_act != nullptr, row_call(gy, ya, w, nullptr, gx, nullptr, ws, ws_bytes));
+    if (!ws || ws_bytes < pl.bytes || !al16(ws)) return MS_ERR_WORKSPACE;
+    return run_convt(pl, p, RowOps{gy, ya, nullptr, nullptr, nullptr, nullptr, gx, nullptr}, w, ws, s, nullptr);
 }
 
 // workspace: [dWq | split-K slabs of whichever kernel takes the launch]
@@ -1815,58 +1747,36 @@ size_t msm_convt_bwd_weight_ws(const ConvP& p) {
 }
 
 const char* msm_convt_bwd_weight_name(const ConvP& p) {
+    static thread_local char buf[MS_PROFILE_NAME_MAX];
     if (msw_convt_ws(p) > 0 && p.act != MS_ACT_TANH) {
-        static thread_local char buf[64];
         snprintf(buf, sizeof(buf), "k_wgrad_rows<3, %d, true, %d, 3, %d>", p.Cout >= 128 ? 2 : 1, p.Lout <= 32 ? 8 : 16, p.stride);
         return buf;
     }
-    return kname("k_igemm_wgrad", plan_convt_wgrad(p).w.cfg, 3, "");
+    const ConvtWgradPlan pl = plan_convt_wgrad(p);
+    return named(launch_wgrad(pl.w, 3, false, pl.q, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, buf), buf);
 }
 
 // gw_T via the phase-split weight-grad GEMM, then un-packed into (Cin_T, Cout_T, K)
 int msm_convt1d_bwd_weight(const ConvP& p, const float* x, const float* gy, const float* y_act,
                            float* gw, float beta, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int S = p.stride, CinT = p.Cout, CoutT = p.Cin, LinT = p.Lout;
+    const int S = p.stride, CinT = p.Cout, CoutT = p.Cin;
     const ConvtWgradPlan pl = plan_convt_wgrad(p);
     if (!ws || ws_bytes < msm_convt_bwd_weight_ws(p)) return MS_ERR_WORKSPACE;
     float* dwq = (float*)ws;
     const size_t dbytes = align16(pl.dwq_floats * sizeof(float));
     float* partial = (float*)((char*)ws + dbytes);
-    const size_t gtotal0 = (size_t)CinT * CoutT * p.K;
     // row-tile form (wgrad_rows.hip) where it applies; the im2col form below otherwise
-    if (msw_convt_dwq(p, x, gy, y_act, dwq, partial, ws_bytes - dbytes, s) == MS_OK) {
-        unsigned nb0 = (unsigned)((gtotal0 + 255) / 256);
-        if (nb0 > 4096) nb0 = 4096;
-        hipLaunchKernelGGL(k_unpack_convt_gw, dim3(nb0), dim3(256), 0, s, dwq, gw, CinT, CoutT, p.K, S, p.pad, beta);
-        MS_CHECK_LAUNCH();
-        return MS_OK;
-    }
-    IgP q;
-    q.B = p.B; q.CK = CoutT * S; q.L = LinT; q.M = CinT; q.dil = 1; q.off0 = -1;
-    q.pad_mode = MS_PAD_ZERO; q.act = MS_ACT_NONE; q.in_act = p.act; q.slope = p.slope;
-    q.N = p.B * LinT; q.KG = q.CK * 3; q.in_s = S;
-    const int NG = q.CK * 3;
-    dim3 grid((unsigned)ms_ceil_div(NG, pl.w.bn), (unsigned)ms_ceil_div(CinT, pl.w.bm), (unsigned)pl.w.nsplit);
-    // A operand = x_T (no activation), B operand = phase-split gy with act'(y_T)
-#define MS_TWG(WGM, WGN, TM, TN)                                                                     \
-    hipLaunchKernelGGL((k_igemm_wgrad<WGM, WGN, TM, TN, 3>), grid, dim3(256), 0, s, q, pl.w.cps, gy, \
-                       y_act, x, p.in_act ? x : (const float*)nullptr,                               \
-                       p.in_act ? MS_MOD_LRELU_FWD : 0, partial, pl.w.stride_floats)
-    if (pl.w.cfg == CFG_128x128) MS_TWG(2, 2, 2, 2);
-    else if (pl.w.cfg == CFG_64x64) MS_TWG(2, 2, 1, 1);
-    else if (pl.w.cfg == CFG_32x128) MS_TWG(1, 4, 1, 1);
-    else MS_TWG(1, 4, 1, 2);
-#undef MS_TWG
-    MS_CHECK_LAUNCH();
-    {
-        const int rc = msm_wgrad_reduce(partial, pl.w.stride_floats, pl.w.nsplit, (size_t)CinT * NG, CinT, dwq,
-                                        (float*)nullptr, 0.f, s);
+    int rc = msw_convt_dwq(p, x, gy, y_act, dwq, partial, ws_bytes - dbytes, s);
+    if (rc != MS_OK) {
+        // A operand = x_T (no activation), B operand = phase-split gy with act'(y_T)
+        rc = launch_wgrad(pl.w, 3, false, pl.q, gy, y_act, x, p.in_act ? x : nullptr, p.in_act ? MS_MOD_LRELU_FWD : 0, partial, s,
+                          nullptr);
+        if (rc == MS_OK)
+            rc = msm_wgrad_reduce(partial, pl.w.stride_floats, pl.w.nsplit, (size_t)CinT * pl.q.KG, CinT, dwq, nullptr, 0.f, s);
         if (rc != MS_OK) return rc;
     }
-    const size_t gtotal = (size_t)CinT * CoutT * p.K;
-    unsigned nb = (unsigned)((gtotal + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_unpack_convt_gw, dim3(nb), dim3(256), 0, s, dwq, gw, CinT, CoutT, p.K, S, p.pad, beta);
+    hipLaunchKernelGGL(k_unpack_convt_gw, blocks256((size_t)CinT * CoutT * p.K, 4096), dim3(256), 0, s, dwq, gw, CinT, CoutT, p.K,
+                       S, p.pad, beta);
     MS_CHECK_LAUNCH();
     return MS_OK;
 }

@@ -455,12 +455,14 @@ __global__ __launch_bounds__(256) void k_conv_rows2(Row2P p, const float* __rest
 
 template <int WGM, int WGN, int TM, int TN, int K, int CC, int AM, int EPI_S, int IN_S = 1>
 int launch_inst(const Row2P& p, const float* X, const float* Xact, const float* W, const float* bias,
-                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s) {
+                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     size_t fl = (size_t)2 * (BM * (CC * K + 1) + CC * p.PX);
     if (EPI_S == 0 && fl < (size_t)BM * (BN + 4)) fl = (size_t)BM * (BN + 4);   // output transpose tile
     const size_t lds = (fl + 256) * sizeof(float);
     if (lds > 150 * 1024) return MS_ERR_UNSUPPORTED;
+    if (ms_name_or_note(name, 0, "k_conv_rows2<%d, %d, %d, %d, %d, %d, %d, %d, %d>", WGM, WGN, TM, TN, K, CC, AM, EPI_S, IN_S))
+        return MS_OK;
     static unsigned long long attr_set = 0;                    // > 64 KiB of dynamic LDS needs the opt-in once
     if (ms_first_on_device(attr_set)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_rows2<WGM, WGN, TM, TN, K, CC, AM, EPI_S, IN_S>),
@@ -469,7 +471,6 @@ int launch_inst(const Row2P& p, const float* X, const float* Xact, const float* 
     }
     Row2P pp = p;
     pp.scratch_off = (int)fl;
-    ms_note_kernel(0, "k_conv_rows2<%d, %d, %d, %d, %d, %d, %d, %d, %d>", WGM, WGN, TM, TN, K, CC, AM, EPI_S, IN_S);
     hipLaunchKernelGGL((k_conv_rows2<WGM, WGN, TM, TN, K, CC, AM, EPI_S, IN_S>), grid, dim3(256), lds, s, pp, X, Xact,
                        W, bias, res, Y, Yact);
     MS_CHECK_LAUNCH();
@@ -478,12 +479,12 @@ int launch_inst(const Row2P& p, const float* X, const float* Xact, const float* 
 
 template <int K, int CC, int AM, int EPI_S, int IN_S = 1>
 int launch_tile(int tile, const Row2P& p, const float* X, const float* Xact, const float* W,
-                const float* bias, const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s) {
+                const float* bias, const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
     switch (tile) {
-        case MSR2_128x128: return launch_inst<2, 2, 2, 2, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
-        case MSR2_64x128: return launch_inst<2, 2, 1, 2, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
-        case MSR2_64x64: return launch_inst<2, 2, 1, 1, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
-        case MSR2_32x256: return launch_inst<1, 4, 1, 2, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
+        case MSR2_128x128: return launch_inst<2, 2, 2, 2, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+        case MSR2_64x128: return launch_inst<2, 2, 1, 2, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+        case MSR2_64x64: return launch_inst<2, 2, 1, 1, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+        case MSR2_32x256: return launch_inst<1, 4, 1, 2, K, CC, AM, EPI_S, IN_S>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
         default: return MS_ERR_UNSUPPORTED;
     }
 }
@@ -527,26 +528,25 @@ bool msr2_supported(int tile, int K, int CC, int act_mode, int epi_s, const Row2
 
 int msr2_launch(int tile, int K, int CC, int act_mode, int epi_s, const Row2P& p, const float* X,
                 const float* Xact, const float* W, const float* bias, const float* res, float* Y,
-                float* Yact, unsigned gx, unsigned gy, unsigned gz, hipStream_t s, int in_s) {
-    const dim3 grid(gx, gy, gz);
-    if (in_s == 0) return launch_tile<5, 16, 1, 0, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (in_s == 8 && act_mode == 2) return launch_tile<2, 8, 2, 0, 8>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (in_s == 2 && act_mode == 2) return launch_tile<2, 8, 2, 0, 2>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (in_s == 8) return launch_tile<2, 8, 0, 0, 8>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (in_s == 2) return launch_tile<2, 8, 0, 0, 2>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
+                float* Yact, dim3 grid, hipStream_t s, int in_s, char* name) {
+    if (in_s == 0) return launch_tile<5, 16, 1, 0, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (in_s == 8 && act_mode == 2) return launch_tile<2, 8, 2, 0, 8>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (in_s == 2 && act_mode == 2) return launch_tile<2, 8, 2, 0, 2>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (in_s == 8) return launch_tile<2, 8, 0, 0, 8>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (in_s == 2) return launch_tile<2, 8, 0, 0, 2>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
 #define MSR2_HALF(A)                                                                                              \
     if (K == 2 && CC == 8 && act_mode == A && tile == MSR2_128x128) {                                            \
-        if (epi_s == 8) return launch_inst<2, 2, 2, 2, 2, 8, A, 8>(p, X, Xact, W, bias, res, Y, Yact, grid, s);  \
-        if (epi_s == 2) return launch_inst<2, 2, 2, 2, 2, 8, A, 2>(p, X, Xact, W, bias, res, Y, Yact, grid, s);  \
+        if (epi_s == 8) return launch_inst<2, 2, 2, 2, 2, 8, A, 8>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
+        if (epi_s == 2) return launch_inst<2, 2, 2, 2, 2, 8, A, 2>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
     }                                                                                                            \
     if (K == 2 && CC == 8 && act_mode == A && tile == MSR2_64x128) {   /* 64 x 128 as 1 x 4 waves of 64 x 32 */  \
-        if (epi_s == 8) return launch_inst<1, 4, 2, 1, 2, 8, A, 8>(p, X, Xact, W, bias, res, Y, Yact, grid, s);  \
-        if (epi_s == 2) return launch_inst<1, 4, 2, 1, 2, 8, A, 2>(p, X, Xact, W, bias, res, Y, Yact, grid, s);  \
+        if (epi_s == 8) return launch_inst<1, 4, 2, 1, 2, 8, A, 8>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
+        if (epi_s == 2) return launch_inst<1, 4, 2, 1, 2, 8, A, 2>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
     }
     MSR2_HALF(0)
     MSR2_HALF(3)
 #undef MSR2_HALF
-#define MSR2_GO(KK, C, A, E) return launch_tile<KK, C, A, E>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s)
+#define MSR2_GO(KK, C, A, E) return launch_tile<KK, C, A, E>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name)
     if (K == 3 && epi_s == 0) {
         if (CC == 8) { if (act_mode) MSR2_GO(3, 8, 1, 0); else MSR2_GO(3, 8, 0, 0); }
         if (CC == 16) { if (act_mode) MSR2_GO(3, 16, 1, 0); else MSR2_GO(3, 16, 0, 0); }

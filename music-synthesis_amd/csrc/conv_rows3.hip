@@ -763,10 +763,12 @@ size_t ldsp_bytes(const Row2P& p) {
 
 template <int WGM, int TM, int TN, int K, int AM, int HS = 0, bool INA = false, int DBG = 0>
 int launch_pair(const Row2P& p, const float* X, const float* Xact, const float* W, const float* bias,
-                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s) {
+                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
     const size_t by = ldsp_bytes<WGM * TM * 32, HS ? 2 : K>(p);
     const size_t lds = by + 512 * 8;
     if (lds > 158 * 1024) return MS_ERR_UNSUPPORTED;
+    if (ms_name_or_note(name, 6, "k_conv_rows3p<%d, %d, %d, %d, %d, %d, %s>", WGM, TM, TN, K, AM, HS, INA ? "true" : "false"))
+        return MS_OK;
     static unsigned long long attr_set = 0;
     if (ms_first_on_device(attr_set)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_rows3p<WGM, TM, TN, K, AM, HS, INA, DBG>),
@@ -775,7 +777,6 @@ int launch_pair(const Row2P& p, const float* X, const float* Xact, const float* 
     }
     Row2P pp = p;
     pp.scratch_off = (int)by;
-    ms_note_kernel(6, "k_conv_rows3p<%d, %d, %d, %d, %d, %d, %s>", WGM, TM, TN, K, AM, HS, INA ? "true" : "false");
     hipLaunchKernelGGL((k_conv_rows3p<WGM, TM, TN, K, AM, HS, INA, DBG>), grid, dim3(512), lds, s, pp, X, Xact, W, bias, res,
                        Y, Yact);
     MS_CHECK_LAUNCH();
@@ -793,10 +794,12 @@ size_t lds_bytes(const Row2P& p) {
 
 template <int WGM, int WGN, int TM, int TN, int K, int AM, bool VEC>
 int launch_inst(const Row2P& p, const float* X, const float* Xact, const float* W, const float* bias,
-                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s) {
+                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
     const size_t by = lds_bytes<WGM, WGN, TM, TN, K, AM>(p);
     const size_t lds = by + 256 * 8;
     if (lds > 156 * 1024) return MS_ERR_UNSUPPORTED;
+    if (ms_name_or_note(name, 6, "k_conv_rows3<%d, %d, %d, %d, %d, %d, %s>", WGM, WGN, TM, TN, K, AM, VEC ? "true" : "false"))
+        return MS_OK;
     static unsigned long long attr_set = 0;                    // > 64 KiB of dynamic LDS needs the opt-in once
     if (ms_first_on_device(attr_set)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_rows3<WGM, WGN, TM, TN, K, AM, VEC>),
@@ -805,7 +808,6 @@ int launch_inst(const Row2P& p, const float* X, const float* Xact, const float* 
     }
     Row2P pp = p;
     pp.scratch_off = (int)by;
-    ms_note_kernel(6, "k_conv_rows3<%d, %d, %d, %d, %d, %d, %s>", WGM, WGN, TM, TN, K, AM, VEC ? "true" : "false");
     hipLaunchKernelGGL((k_conv_rows3<WGM, WGN, TM, TN, K, AM, VEC>), grid, dim3(256), lds, s, pp, X, Xact, W, bias,
                        res, Y, Yact);
     MS_CHECK_LAUNCH();
@@ -816,18 +818,18 @@ bool rows_vec(const Row2P& p) { return p.L % 4 == 0 && p.Lt % 4 == 0; }
 
 template <int K, int AM>
 int launch_tile(int tile, const Row2P& p, const float* X, const float* Xact, const float* W, const float* bias,
-                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s) {
+                const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
     if (rows_vec(p)) {
         switch (tile) {
-            case MSR2_128x128: return launch_inst<2, 2, 2, 2, K, AM, true>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
-            case MSR2_64x128: return launch_inst<2, 2, 1, 2, K, AM, true>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
-            case MSR2_64x64: return launch_inst<2, 2, 1, 1, K, AM, true>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
+            case MSR2_128x128: return launch_inst<2, 2, 2, 2, K, AM, true>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+            case MSR2_64x128: return launch_inst<2, 2, 1, 2, K, AM, true>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+            case MSR2_64x64: return launch_inst<2, 2, 1, 1, K, AM, true>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
             default: return MS_ERR_UNSUPPORTED;
         }
     }
     switch (tile) {      // rows of any length (dword loader / epilogue)
-        case MSR2_64x128: return launch_inst<2, 2, 1, 2, K, AM, false>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
-        case MSR2_64x64: return launch_inst<2, 2, 1, 1, K, AM, false>(p, X, Xact, W, bias, res, Y, Yact, grid, s);
+        case MSR2_64x128: return launch_inst<2, 2, 1, 2, K, AM, false>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+        case MSR2_64x64: return launch_inst<2, 2, 1, 1, K, AM, false>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
         default: return MS_ERR_UNSUPPORTED;
     }
 }
@@ -855,18 +857,20 @@ bool msr3_supported(int tile, int K, int act_mode, int epi_s, const Row2P& p, in
 }
 
 int msr3_launch(int tile, int K, int act_mode, const Row2P& p, const float* X, const float* Xact, const float* W,
-                const float* bias, const float* res, float* Y, float* Yact, unsigned gx, unsigned gy, unsigned gz,
-                hipStream_t s) {
-    const dim3 grid(gx, gy, gz);
-    if (K == 3 && act_mode == 0) return launch_tile<3, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (K == 3 && act_mode == 1) return launch_tile<3, 1>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (K == 5 && act_mode == 0) return launch_tile<5, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
-    if (K == 5 && act_mode == 1) return launch_tile<5, 1>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s);
+                const float* bias, const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
+    if (K == 3 && act_mode == 0) return launch_tile<3, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (K == 3 && act_mode == 1) return launch_tile<3, 1>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (K == 5 && act_mode == 0) return launch_tile<5, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (K == 5 && act_mode == 1) return launch_tile<5, 1>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
     return MS_ERR_UNSUPPORTED;
 }
 
 // Paired eight-wave form (k_conv_rows3p): bm = 128 (K = 3) or 64 rows x two adjacent 128-column tiles per
-// workgroup.  The caller uses it where the grid still fills the chip: msr3p_grid gives the workgroup count.
+// workgroup.  The caller uses it where the grid still fills the chip: msr3p_grid gives the workgroups.
+dim3 msr3p_grid(int bm, const Row2P& p, unsigned gz) {
+    const unsigned ntiles = p.R == 1 ? (unsigned)(p.B * p.tiles_per_row) : (unsigned)((p.B + p.R - 1) / p.R);
+    return dim3((ntiles + 1) / 2, (unsigned)((p.M + bm - 1) / bm), gz);
+}
 bool msr3p_supported(int bm, int K, int act_mode, int epi_s, const Row2P& p, int in_s) {
     if (!ms_switch_on("MSYNTH_ROWS3P")) return false;    // tuning / test switch (0: four-wave kernel only)
     if (bm != 32 && bm != 64 && bm != 128) return false;
@@ -879,10 +883,8 @@ bool msr3p_supported(int bm, int K, int act_mode, int epi_s, const Row2P& p, int
 }
 
 int msr3p_launch(int bm, int K, int act_mode, const Row2P& p, const float* X, const float* Xact, const float* W,
-                 const float* bias, const float* res, float* Y, float* Yact, unsigned gz, hipStream_t s) {
-    const unsigned ntiles = p.R == 1 ? (unsigned)(p.B * p.tiles_per_row) : (unsigned)((p.B + p.R - 1) / p.R);
-    const dim3 grid((ntiles + 1) / 2, (unsigned)((p.M + bm - 1) / bm), gz);
-#define MS3P(WGM_, TM_, TN_, K_, A_) return launch_pair<WGM_, TM_, TN_, K_, A_>(p, X, Xact, W, bias, res, Y, Yact, grid, s)
+                 const float* bias, const float* res, float* Y, float* Yact, dim3 grid, hipStream_t s, char* name) {
+#define MS3P(WGM_, TM_, TN_, K_, A_) return launch_pair<WGM_, TM_, TN_, K_, A_>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name)
     if (bm == 128) {
         if (K == 3 && act_mode == 0) MS3P(2, 2, 2, 3, 0);
         if (K == 3 && act_mode == 1) MS3P(2, 2, 2, 3, 1);
@@ -902,7 +904,7 @@ int msr3p_launch(int bm, int K, int act_mode, const Row2P& p, const float* X, co
 }
 
 // Transposed-conv forward on the paired kernel (HS form).  p: the row description of the mirrored conv with the
-// 3-column window (rows2_pick(.., K = 2, ..)), p.M = Cout * S GEMM rows, p.KG = 2 CK; W packed by k_pack_convt_w2.
+// 3-column window (conv_mfma.hip plan_rows, two-tap form), p.M = Cout * S GEMM rows, p.KG = 2 CK; W packed by k_pack_convt_w2.
 bool msr3p_convt_supported(int bm, int S, const Row2P& p) {
     if (!ms_switch_on("MSYNTH_ROWS3P")) return false;
     if (!ms_switch_on("MSYNTH_CONVT3")) return false;    // tuning / test switch (0: fp32-MFMA transposed-conv kernel)
@@ -916,11 +918,9 @@ bool msr3p_convt_supported(int bm, int S, const Row2P& p) {
 }
 
 int msr3p_convt_launch(int bm, int S, bool in_act, const Row2P& p, const float* X, const float* W, const float* bias,
-                       float* Y, unsigned gz, hipStream_t s) {
-    const unsigned ntiles = p.R == 1 ? (unsigned)(p.B * p.tiles_per_row) : (unsigned)((p.B + p.R - 1) / p.R);
-    const dim3 grid((ntiles + 1) / 2, (unsigned)((p.M + bm - 1) / bm), gz);
+                       float* Y, dim3 grid, hipStream_t s, char* name) {
 #define MS3T(WGM_, TM_, S_, IA_) \
-    return launch_pair<WGM_, TM_, 2, 3, 0, S_, IA_>(p, X, nullptr, W, bias, nullptr, Y, nullptr, grid, s)
+    return launch_pair<WGM_, TM_, 2, 3, 0, S_, IA_>(p, X, nullptr, W, bias, nullptr, Y, nullptr, grid, s, name)
     if (bm == 128) {
         if (S == 8) { if (in_act) MS3T(2, 2, 8, true); MS3T(2, 2, 8, false); }
         if (in_act) MS3T(2, 2, 2, true);

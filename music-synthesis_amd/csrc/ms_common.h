@@ -28,6 +28,10 @@ static inline bool ms_switch_on(const char* name) { return ms_switch_int(name, 1
 // (block-scaled two-piece fp16 split), 0 (fp32-input MFMA or vector FMA).  ms_profile_take() hands both to the caller, so a
 // profiler line is matched to a layer and priced on the right pipe without re-deriving the dispatch.  No-op outside a session.
 void ms_note_kernel(int products, const char* fmt, ...);
+// One spelling per kernel template: a launcher of the row-tile family (conv_mfma.hip, conv_rows2.hip, conv_rows3.hip) formats
+// its instantiation here and nowhere else.  name == nullptr: a launch -- noted as ms_note_kernel does, returns false.  Otherwise
+// the caller is a name query: the spelling goes to name[MS_PROFILE_NAME_MAX] and the launcher returns without launching (true).
+bool ms_name_or_note(char* name, int products, const char* fmt, ...);
 
 // Profiling aid (ms_profile_kernels / ms_profile_take, api.hip): while a thread is in profile mode every kernel launch of the
 // library carries a start / stop event pair (hipExtLaunchKernelGGL: the events take the dispatch's own begin / end timestamps,

@@ -626,8 +626,7 @@ case("resample_up_and_normalize", ("ms_resample_sinc_fwd", "ms_peak_normalize"),
 # ================================================================ (a) (b) convs and transposed convs through the dispatch plan
 
 def _stem(name):
-    # (k_conv_rows3p is the paired form of k_conv_rows3: one stem, as in tests/test_gpu_dispatch.py)
-    return name.split("<")[0].strip().replace("k_conv_rows3p", "k_conv_rows3")
+    return name.split("<")[0].strip()
 
 
 def profiled(fn, notes):
@@ -843,8 +842,7 @@ for _w in (0, 1, 2):
     case("conv_%s_DIRECT_all_plus4" % "FDW"[_w], _CONV_SYMS[_w], conv_case, _S["direct_s2"], _w, None,
          {"x": 4, "w": 4, "y": 4, "y_act": 4, "residual": 8, "gy": 4, "gx": 12, "gx_add": 8, "gw": 4, "gb": 4}, "plus4")
 # F_MFMA with the weights at a 4-byte address: the row kernels read them 16 bytes at a time and are not taken
-# (msm_conv1d_fwd tests w), the im2col kernel behind reads dwords
-# (that launcher leaves the route's note in place, so no other stem is required here)
+# (conv_mfma.hip plan_fwd tests w), the im2col kernel behind reads dwords
 case("conv_F_MFMA_declines_w_plus4", "ms_conv1d_fwd", conv_case, _S["mfma_m48"], 0, None, {"w": 4})
 
 
@@ -869,9 +867,8 @@ for _nm, _shape, _which, _ops in (("F_G3", "g3_vec_l512", 0, ("x", "y")), ("D_G3
                "W_K5_split": {"x": r"k5_split<false>", "gy": r"k5_split<false>"}}.get(_nm, {}).get(_op)
         case("conv_%s_dword_form_%s_plus4" % (_nm, _op), _CONV_SYMS[_which], conv_case, _S[_shape], _which, None, {_op: 4}, "exact",
              None, 0, MS_OK, _dw)
-# the row-tile routes F_MFMA / D_MFMA pick the pipelined kernels only for 16-byte operands (conv_mfma.hip rows2_pick tests x, w,
-# y, y_act, residual); behind them k_conv_mfma_rows reads and writes these tensors as dwords.  (These launchers record no
-# instantiation: the note stays the route's.)
+# the row-tile routes F_MFMA / D_MFMA pick the pipelined kernels only for 16-byte operands (conv_mfma.hip plan_rows tests x, w,
+# y, y_act, residual); behind them k_conv_mfma_rows reads and writes these tensors as dwords.
 for _op in ("x", "y", "y_act", "residual"):
     case("conv_F_MFMA_rows_%s_plus4" % _op, "ms_conv1d_fwd", conv_case, _S["k3_l16_rows"], 0, None, {_op: 4})
 for _op in ("gy", "y_act", "gx", "gx_add"):
@@ -967,7 +964,7 @@ _T = {
 CONVT_ROUTES = [
     ("TF_THIN", "thin_l131", 0, "k_convt1_fwd"), ("TF_LANES", "lanes_s8", 0, "k_convt_lanes"), ("TF_MFMA", "rows_s8_b32", 0, "k_conv_rows2"),
     ("TF_DIRECT", "direct", 0, "k_conv1d_bwd_data_direct"),
-    ("TD_MFMA", "s2_small", 1, "k_conv_rows2"), ("TD_MFMA_s8", "w8_l32", 1, "k_conv_rows2"), ("TD_CONV_MFMA", "s1_k3_c32", 1, None),
+    ("TD_MFMA", "s2_small", 1, "k_conv_rows2"), ("TD_MFMA_s8", "w8_l32", 1, "k_conv_rows2"), ("TD_CONV_MFMA", "s1_k3_c32", 1, "k_conv_mfma_rows"),
     ("TD_CONV_DIRECT", "direct", 1, "k_conv1d_fwd_direct"), ("TD_CONV_DIRECT_thin", "thin_l131", 1, "k_conv1d_fwd_direct"),
     ("TW_THIN", "thin_l131", 2, "k_convt1_wgrad"), ("TW_8", "w8_l32", 2, "k_wgrad_convt8_split"), ("TW_2S", "t2s", 2, "k_wgrad_convt2_short"),
     ("TW_MFMA", "s2_128_64", 2, "k_igemm_wgrad"), ("TW_CONV_MFMA", "s1_k3", 2, "k_igemm_wgrad_v4"),
@@ -988,7 +985,7 @@ case("convt_TF_MFMA_s2_declines_y_plus4", "ms_convt1d_fwd", convt_case, ("mc_ct_
 for _route, _shape in (("TW_8", "w8_l32"), ("TW_2S", "t2s")):
     for _op in ("x", "gy", "y_act"):
         case("convt_%s_declines_%s_plus4" % (_route, _op), "ms_convt1d_bwd_weight", convt_case, _T[_shape], 2, None, {_op: 4})
-# TD_MFMA behind rows2_pick: k_conv_mfma_rows reads the phase-split gradient and writes gx as dwords
+# TD_MFMA behind plan_rows: k_conv_mfma_rows reads the phase-split gradient and writes gx as dwords
 for _op in ("gy", "y_act", "gx"):
     case("convt_TD_MFMA_rows_%s_plus4" % _op, "ms_convt1d_bwd_data", convt_case, _T["s2_small"], 1, None, {_op: 4})
 case("convt_DIRECT_all_plus4", _CONVT_SYMS, lambda: [convt_case(_T["direct"], wh, None, {"x": 4, "w": 4, "y": 4, "gy": 4, "y_act": 8,
