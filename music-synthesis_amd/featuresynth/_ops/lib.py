@@ -1,4 +1,4 @@
-"""ctypes binding of libmsynth_hip.so (the C ABI declared in include/msynth.h).
+"""ctypes binding of libmsynth_hip.so (the C ABI declared in include/msynth.h and include/msynth_bands.h).
 
 There is no CPU fallback: if the shared library is missing, or an op is handed a
 tensor that is not a contiguous fp32 HIP-device tensor, a RuntimeError is raised.
@@ -237,6 +237,23 @@ SIGNATURES = {
 }
 COMM_ID_BYTES = 128
 
+BAND_MAX = 8
+
+
+class BandDesc(ctypes.Structure):               # ms_band_desc (include/msynth_bands.h)
+    _fields_ = [("count", _c_int), ("lowest", _c_int), ("size", _c_int * BAND_MAX), ("data", _vp * BAND_MAX)]
+
+
+# name -> (restype, argtypes); every symbol include/msynth_bands.h declares
+BAND_SIGNATURES = {
+    "ms_band_supported": (_c_int, [_c_int, ctypes.POINTER(BandDesc)]),
+    "ms_band_workspace_bytes": (_sz, [_c_int, _c_int, ctypes.POINTER(BandDesc)]),
+    "ms_band_decompose_fwd": (_c_int, [_vp, _c_int, _c_int, ctypes.POINTER(BandDesc), _vp, _sz, _vp]),
+    "ms_band_decompose_bwd": (_c_int, [ctypes.POINTER(BandDesc), _c_int, _c_int, _vp, _vp, _sz, _vp]),
+    "ms_band_recompose_fwd": (_c_int, [ctypes.POINTER(BandDesc), _c_int, _c_int, _vp, _vp, _sz, _vp]),
+    "ms_band_recompose_bwd": (_c_int, [_vp, _c_int, _c_int, ctypes.POINTER(BandDesc), _vp, _sz, _vp]),
+}
+
 _LIB = None
 
 
@@ -250,7 +267,7 @@ def load():
                 "`make -C music-synthesis_amd/csrc` or __graft_entry__.build(). There is no CPU "
                 "or PyTorch fallback for the hot path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(BAND_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

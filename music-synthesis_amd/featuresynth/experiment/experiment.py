@@ -9,7 +9,8 @@ Differences, all additive:
   * `checkpoint` / `resume` can also carry the optimizer state (the reference drops it);
   * under torch.distributed, `to(device)` broadcasts rank 0's parameters so replicas start equal,
     and `synthetic_batch_stream` seeds each rank differently;
-  * the file / LMDB data layer (`batch_stream`, `from_audio` on zounds objects, reports) is out
+  * `audio_repr_class` (featuresynth.audio) is optional: None keeps samples as they are;
+  * the file / LMDB data layer (`batch_stream`, reports) is out
     of scope: `batch_stream` raises and points at `synthetic_batch_stream`.
 """
 import os
@@ -137,10 +138,25 @@ class Experiment(BaseGanExperiment):
         return self
 
     # ---- batches
+    def from_audio(self, samples, sr):
+        """reference :195-196; needs an audio_repr_class (featuresynth.audio: RawAudio, MultiScale)"""
+        if self._audio_repr_class is None:
+            raise NotImplementedError("Experiment.from_audio: no audio_repr_class was given")
+        return self._audio_repr_class.from_audio(samples, sr)
+
+    def audio_representation(self, data, sr):
+        """reference :198-199"""
+        if self._audio_repr_class is None:
+            raise NotImplementedError("Experiment.audio_representation: no audio_repr_class was given")
+        return self._audio_repr_class(data, sr)
+
     def preprocess_batch(self, batch):
-        """RawAudio is the identity representation (audio/representation.py:38-54): samples stay
-        (B, 1, N) float32, features (B, channels, frames)."""
+        """Without an audio_repr_class: RawAudio, the identity representation (audio/representation.py:38-54): samples
+        stay (B, 1, N) float32, features (B, channels, frames).  With one (reference :201-205): the samples become
+        from_audio(samples, samplerate).data -- for MultiScale a dict of bands -- and the features pass through."""
         samples, features = batch
+        if self._audio_repr_class is not None:
+            return self.from_audio(samples, self.samplerate).data, features
         return np.asarray(samples, dtype=np.float32), np.asarray(features, dtype=np.float32)
 
     def batch_stream(self, path, pattern, batch_size, feature_spec=None):
