@@ -66,10 +66,9 @@ __global__ __launch_bounds__(256) void k_atom_wmax(AtomPackTable t) {
     const int n = jb.C * jb.C * 3, per = (n + W_NPART - 1) / W_NPART;
     const int lo = part * per, hi = lo + per < n ? lo + per : n;
     float m = 0.f;
-    typedef float f32x4w __attribute__((ext_vector_type(4), aligned(4)));      // (16 bytes per lane at any 4-byte aligned address)
     int i = lo + 4 * (int)threadIdx.x;
     for (; i + 3 < hi; i += 1024) {
-        const f32x4w v = *reinterpret_cast<const f32x4w*>(w + i);
+        const f32x4u v = *reinterpret_cast<const f32x4u*>(w + i);
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (; i < hi; ++i) m = fmaxf(m, fabsf(w[i]));
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(256) void k_atom_pack(AtomPackTable t) {
     float WS = 1.f, iWS = 1.f;
     if (jb.np == 2) {
         float* tail = atom_image_tail(jb);
-        weight_scale(tail + conv * W_NPART, WS, iWS);
+        weight_scale(weight_max16(tail + conv * W_NPART), WS, iWS);
         if (ms == 0 && chunk == 0 && tap == 0 && lane == 0) tail[2 * W_NPART + conv] = iWS;
     }
     unsigned pc[3][4];
@@ -205,7 +204,6 @@ __global__ __launch_bounds__(64 * NW, 2) void k_atom_fwd(AtomP p, const float* _
     constexpr int NXA = NTP + 22;                    // LDS columns per chunk (dilation <= 9: NTP + 2 d + 3 used)
     constexpr int XCS = NXA * XRS;                   // chunk stride of the x window (compile-time: LDS offsets fold into the instructions)
     constexpr int TCS = XCS;                         // the t tile aliases the window, same strides (it is read up to column NTP - 1 + 2 h2)
-    constexpr unsigned OOB = 0xF0000000u;
     const int ntiles = p.B * p.tiles_per_row;
 
     // Operands and results go through buffer descriptors: a lane that is out of the tensor carries an out-of-range

@@ -154,9 +154,7 @@ __global__ __launch_bounds__(256) void k_audio2mel_bwd_frame(const float* __rest
     // d/d u[n] = Re sum_k G[k] exp(+2 pi i k n / n_fft), bit-reversed order out (so the gradient spectrum is written
     // in place above, with no permutation)
     ms_frame_ifft_bitrev(n_fft, re, im);
-    float* gf = gframes + ((size_t)b * frames + fr) * n_fft;
-    for (int n = threadIdx.x; n < n_fft; n += 256)
-        gf[n] = window[n] * re[(int)(__brev((unsigned)n) >> (32 - log2n))];
+    ms_frame_store_bitrev(window, re, n_fft, log2n, gframes + ((size_t)b * frames + fr) * n_fft);
 }
 
 // grad_audio[b][s] = sum over the frames f that cover sample s (s - f*hop in [0, n_fft)), in increasing f;
@@ -165,15 +163,8 @@ __global__ __launch_bounds__(256) void k_audio2mel_bwd_gather(const float* __res
                                                              int hop, int frames, float* __restrict__ grad_audio) {
     const int b = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
     if (s >= N) return;
-    const int f_lo = s < n_fft ? 0 : (s - n_fft) / hop + 1;
-    const int f_hi = min(frames - 1, s / hop);
-    const float* g = gframes + (size_t)b * frames * n_fft;
-    float acc = 0.f;
-    for (int f = f_lo; f <= f_hi; ++f) acc += g[(size_t)f * n_fft + (s - f * hop)];
-    grad_audio[(size_t)b * N + s] = acc;
+    grad_audio[(size_t)b * N + s] = ms_frames_over(gframes + (size_t)b * frames * n_fft, s, n_fft, hop, frames);
 }
-
-int a2m_log2(int n_fft) { return ms_frame_log2(n_fft); }
 
 const size_t A2M_BWD_LDS_MAX = 64 * 1024;
 
@@ -192,7 +183,7 @@ int ms_audio2mel_fwd(const float* audio, int32_t B, int32_t N, const float* wind
                      ms_stream_t stream) {
     if (!audio || !window || !mel_basis || !out || B <= 0 || N <= 0 || n_mel <= 0 || hop <= 0)
         return MS_ERR_INVALID_ARG;
-    const int log2n = a2m_log2(n_fft);
+    const int log2n = ms_frame_log2(n_fft);
     if (log2n < 0) return MS_ERR_UNSUPPORTED;
     const int frames = ms_audio2mel_frames(N, n_fft, hop);
     if (frames <= 0) return MS_ERR_INVALID_ARG;
@@ -204,7 +195,7 @@ int ms_audio2mel_fwd(const float* audio, int32_t B, int32_t N, const float* wind
 }
 
 size_t ms_audio2mel_bwd_workspace_bytes(int32_t B, int32_t N, int32_t n_fft, int32_t hop) {
-    if (B <= 0 || a2m_log2(n_fft) < 0) return 0;
+    if (B <= 0 || ms_frame_log2(n_fft) < 0) return 0;
     const int frames = ms_audio2mel_frames(N, n_fft, hop);
     if (frames <= 0) return 0;
     // per-frame gradients, then the supports (int2) of up to n_fft/2+1 filters and of the n_fft/2+1 bins
@@ -216,7 +207,7 @@ int ms_audio2mel_bwd(const float* audio, int32_t B, int32_t N, const float* wind
                      void* workspace, size_t workspace_bytes, ms_stream_t stream) {
     if (!audio || !window || !mel_basis || !grad_out || !grad_audio || B <= 0 || N <= 0 || n_mel <= 0 || hop <= 0)
         return MS_ERR_INVALID_ARG;
-    const int log2n = a2m_log2(n_fft);
+    const int log2n = ms_frame_log2(n_fft);
     if (log2n < 0) return MS_ERR_UNSUPPORTED;
     const int frames = ms_audio2mel_frames(N, n_fft, hop);
     if (frames <= 0) return MS_ERR_INVALID_ARG;

@@ -25,57 +25,31 @@
 //           times the scale leaves [2^8, 2^15)), so the MFMA waves keep accumulating under it and fold their partial sums
 //           into the running fp32 sums only when a scale has moved (rare).
 // The accumulation order differs from the row kernels' (other chunk / slice grouping): results agree to ~1e-7, not bitwise.
-#include "ms_common.h"
+#include "operand_split.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int NP> __host__ __device__ constexpr int xrs() { return NP * 32 + 16; }   // bytes per LDS column of a 16-channel chunk
 constexpr int K5 = 5;
 constexpr int PX_MAX = 350;              // LDS columns per buffer (39.2 / 28 KB; two buffers)
 constexpr int R_MAX = 64;                // batch rows per tile (scale slots)
-constexpr unsigned OOB = 0xF0000000u;
-// NP = 2: weights are packed as the fp16 pieces of S_w w, S_w a power of two taken from the tensor's largest magnitude (it goes
-// to [2^12, 2^13): weights of any magnitude; r04 packed 64 w and overflowed to inf from |w| >= 2^9).  A pack is two launches:
+// NP = 2: the weights are packed as the fp16 pieces of S_w w, S_w the weight_scale of the WHOLE tensor.  A pack is two launches:
 // W_NPART partial maxima into the image's tail (the allocation is sized for three pieces), then the pack proper, whose
 // threads reduce the partials and whose first thread leaves 1 / S_w in the tail for the consuming kernels.
 constexpr int W_NPART = 256;          // partial maxima of a weight tensor (one workgroup each)
-// (called by ALL 256 threads of a pack workgroup, before any of them returns: the first wave reduces the partials, LDS broadcasts)
-__device__ __forceinline__ void weight_scale(const float* __restrict__ pm, float& S, float& invS) {
-    __shared__ float wmax_s;
-    if (threadIdx.x < 64) {
-        float m = fmaxf(fmaxf(pm[threadIdx.x], pm[threadIdx.x + 64]), fmaxf(pm[threadIdx.x + 128], pm[threadIdx.x + 192]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (threadIdx.x == 0) wmax_s = m;
-    }
-    __syncthreads();
-    const float m = wmax_s;
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (266u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 12u) << 23) : 1.f;
-}
 __host__ __device__ inline size_t c5_tail_u4(int M, int CK) { return (size_t)(M / 32) * (CK / 16) * 5 * 2 * 64; }   // end of the NP = 2 data
 
 __global__ __launch_bounds__(256) void k_conv5_wmax(const float* __restrict__ W, size_t n, float* __restrict__ pm) {
+    // (The same body as k_convt_wmax, and the whole-wave shuffle loop spelled out here and in k_conv5_rowmax instead of wave_max():
+    //  moved into a shared inlined function, either comes out of the compiler as the same instructions in another order, and a
+    //  kernel's instructions change only together with a measurement.)
     __shared__ float red[4];
     const size_t per = (n + W_NPART - 1) / W_NPART, lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
     float m = 0.f;
     // 16 bytes per lane at any 4-byte aligned address (a view into a flat parameter bucket): a 21 MB tensor in ~7 us, not 21
-    typedef float f32x4w __attribute__((ext_vector_type(4), aligned(4)));
     size_t i = lo + 4 * (size_t)threadIdx.x;
     for (; i + 3 < hi; i += 1024) {
-        const f32x4w v = *reinterpret_cast<const f32x4w*>(W + i);
+        const f32x4u v = *reinterpret_cast<const f32x4u*>(W + i);
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (; i < hi; ++i) m = fmaxf(m, fabsf(W[i]));                     // (the one thread whose quad crosses the part's end)
@@ -84,46 +58,6 @@ __global__ __launch_bounds__(256) void k_conv5_wmax(const float* __restrict__ W,
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) pm[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-// (a, b) -> NP packed 16-bit pairs: NP = 3 exact bf16 pieces; NP = 2 fp16 pieces a = o[0] + o[1] (22 bits; the caller has
-// scaled a so that its block's largest magnitude sits in [2^8, 2^15): atom_fused.hip)
-template <int NP>
-__device__ __forceinline__ void split_pair(float a, float b, unsigned (&o)[NP]) {
-    const f32x2 v = {a, b};
-    if constexpr (NP == 3) {
-        const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-        const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-        const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-        const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-        const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-        o[0] = __builtin_bit_cast(unsigned, hi);
-        o[1] = __builtin_bit_cast(unsigned, mi);
-        o[2] = __builtin_bit_cast(unsigned, lo);
-    } else {
-        const f16x2 hi = __builtin_convertvector(v, f16x2);
-        const f16x2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), f16x2);
-        o[0] = __builtin_bit_cast(unsigned, hi);
-        o[1] = __builtin_bit_cast(unsigned, lo);
-    }
-}
-
-template <int NP>
-__device__ __forceinline__ void split_quad(const float (&e)[4], uint2 (&o)[NP]) {
-    unsigned a[NP], b[NP];
-    split_pair<NP>(e[0], e[1], a);
-    split_pair<NP>(e[2], e[3], b);
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp) o[pp] = make_uint2(a[pp], b[pp]);
-}
-
-// block scale of values whose largest magnitude is m: S = 2^k with m S in [2^14, 2^15), and 1 / S; 1 for a zero /
-// denormal-range / non-finite maximum (atom_fused.hip)
-__device__ __forceinline__ void block_scale(float m, float& S, float& invS) {
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (268u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 14u) << 23) : 1.f;
 }
 
 // image[ms][chunk][tap][piece][lane] (16 B): rows ms*32 + (lane & 31), contraction channels chunk*16 + 8*(lane >> 5) + 0..7
@@ -139,7 +73,7 @@ __global__ __launch_bounds__(256) void k_conv5_pack(const float* __restrict__ W,
     float WS = 1.f, iWS = 1.f;
     if (np == 2) {
         float* tail = reinterpret_cast<float*>(img + c5_tail_u4(M, CK));
-        weight_scale(pm ? pm : tail, WS, iWS);
+        weight_scale(weight_max256(pm ? pm : tail), WS, iWS);
         if (idx == 0) tail[W_NPART] = iWS;
     }
     if (idx >= total) return;

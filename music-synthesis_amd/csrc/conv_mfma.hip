@@ -19,12 +19,11 @@
 #include <cstdlib>
 #include "conv_mfma.h"
 #include "conv_rows2.h"
+#include "operand_split.h"
 #include <stdio.h>
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int KC = 16;        // GEMM-K elements staged per chunk
 constexpr int KCP = KC + 1;   // odd LDS row stride: conflict-free 32-lane column reads
@@ -828,7 +827,6 @@ __global__ __launch_bounds__(256) void k_igemm_wgrad_v4(IgP p, int chunks_per_sp
     const float* Xq = Xact ? Xact : X;
     const int g_kind = Gact ? g_act : MS_ACT_NONE;
     const int x_kind = Xact ? p.in_act : MS_ACT_NONE;
-    typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
     float4 ra[RA4], rb[RB4];
     auto gload = [&](int chunk) {
         const int kg = chunk * KC + 4 * kq;
@@ -840,7 +838,7 @@ __global__ __launch_bounds__(256) void k_igemm_wgrad_v4(IgP p, int chunks_per_sp
         const float* Xb = X + (size_t)b * p.CK * p.L;
         const float* Xy = Xq + (size_t)b * p.CK * p.L;
         float4 gv[RA4], ga[RA4];
-        f4u xv[RB4], xa[RB4];
+        f32x4u xv[RB4], xa[RB4];
         int s0[RB4];
 #pragma unroll
         for (int r = 0; r < RA4; ++r) {
@@ -853,8 +851,8 @@ __global__ __launch_bounds__(256) void k_igemm_wgrad_v4(IgP p, int chunks_per_sp
             // the 4 taps sit in one row; a window hanging over a row end is re-read element-wise below
             const bool inside = s0[r] >= 0 && s0[r] + 3 < p.L;
             const int off = inside ? boff[r] + s0[r] : boff[r];
-            xv[r] = *reinterpret_cast<const f4u*>(Xb + off);
-            xa[r] = *reinterpret_cast<const f4u*>(Xy + off);
+            xv[r] = *reinterpret_cast<const f32x4u*>(Xb + off);
+            xa[r] = *reinterpret_cast<const f32x4u*>(Xy + off);
         }
 #pragma unroll
         for (int r = 0; r < RB4; ++r) {

@@ -16,10 +16,9 @@
 //   rows of a chunk are the IN_S phases of CC/IN_S channels of a stride-IN_S signal (transposed-conv
 //   backward data), staged from contiguous 16-byte loads of the phase-interleaved spans.
 #include "conv_rows2.h"
+#include "operand_split.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int WGM, int WGN, int TM, int TN, int K, int CC, int AM, int EPI_S, int IN_S = 1>
 __global__ __launch_bounds__(256) void k_conv_rows2(Row2P p, const float* __restrict__ X,

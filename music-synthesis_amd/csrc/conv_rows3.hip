@@ -29,40 +29,13 @@
 // AM 0: forward (W = [M][CK][K]);  AM 1: backward data, LeakyReLU derivative from Xact applied on load,
 // W read in the forward layout W[co][ci][K] (GEMM row = ci, taps flipped).
 #include "conv_rows2.h"
+#include "operand_split.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int CC3 = 16;                     // channels per chunk = one k-step per tap
 constexpr int XRS = 112;                    // bytes per LDS activation column: 3 pieces x 32 + 16
 constexpr int a_row_bytes(int K) { return K * 96 + 16; }
-
-// (a, b) -> three packed bf16 pairs with a = h.lo + m.lo + l.lo exactly (same for b in the high halves)
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-// 4 values (4 consecutive channels of one (row|column, tap)) -> one 8-byte group per piece
-__device__ __forceinline__ void split_quad(const float (&e)[4], uint2 (&o)[3]) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(e[0], e[1], h0, m0, l0);
-    split_pair(e[2], e[3], h1, m1, l1);
-    o[0] = make_uint2(h0, h1);
-    o[1] = make_uint2(m0, m1);
-    o[2] = make_uint2(l0, l1);
-}
 
 constexpr int msr3_nxu(int BN) { return (4 * (BN / 4 + 12) + 255) / 256; }   // activation units per thread
 
@@ -97,7 +70,6 @@ __global__ __launch_bounds__(256) void k_conv_rows3(Row2P p, const float* __rest
     // samples before / behind a row: the zero padding) carries an out-of-range byte offset and the hardware
     // range check returns 0.0f for it -- no per-element selects in the staging code.  The chunk's channel
     // offset travels in the (unchecked) scalar offset.
-    constexpr unsigned OOB = 0xF0000000u;
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, 0x80000000u, 0x00020000);
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, 0x80000000u, 0x00020000);
     const auto rsXa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AM == 1 ? Xact : X), 0, 0x80000000u, 0x00020000);
@@ -172,7 +144,6 @@ __global__ __launch_bounds__(256) void k_conv_rows3(Row2P p, const float* __rest
         bbase[j] = ok ? r * p.SS + tc : 0;
     }
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 ra[NAU][AM == 1 ? 1 : K];
     float rad[NAU][AM == 1 ? 4 * K : 1];
     f32x4 rx[NXU][4], rxa[AM == 1 ? NXU : 1][4];
@@ -431,7 +402,6 @@ __global__ __launch_bounds__(512) void k_conv_rows3p(Row2P p, const float* __res
     if (p.R == 1) { b0 = ti / p.tiles_per_row; t0 = (ti - b0 * p.tiles_per_row) * BN; }
     else { b0 = ti * p.R; t0 = 0; }
 
-    constexpr unsigned OOB = 0xF0000000u;
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, 0x80000000u, 0x00020000);
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, 0x80000000u, 0x00020000);
     const auto rsXa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(AM == 1 ? Xact : X), 0, 0x80000000u, 0x00020000);
@@ -487,7 +457,6 @@ __global__ __launch_bounds__(512) void k_conv_rows3p(Row2P p, const float* __res
         bbase[j] = ok ? r * p.SS + tc : 0;
     }
 
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 ra[AM == 1 ? 1 : KA];
     float rad[AM == 1 ? 4 * K : 1];
     f32x4 rx[4], rxa[AM == 1 ? 4 : 1];

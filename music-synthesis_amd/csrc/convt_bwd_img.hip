@@ -18,42 +18,13 @@
 // with zero halo blocks, split-K slices fill the chip, a finish kernel sums the slabs in slice order.
 // Arithmetic: exact 3-piece bf16 split, six products per multiply, fp32 accumulation (other summation order than the row
 // kernels: agreement ~1e-7).
-#include "ms_common.h"
+#include "operand_split.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int XRS = 112;                 // bytes per LDS block column: 3 pieces x 32 + 16
 constexpr int PX_MAX = 350;              // LDS columns per buffer (39.2 KB; two buffers, two workgroups per CU)
-constexpr unsigned OOB = 0xF0000000u;
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-__device__ __forceinline__ void split_quad(const float (&e)[4], uint2 (&o)[3]) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(e[0], e[1], h0, m0, l0);
-    split_pair(e[2], e[3], h1, m1, l1);
-    o[0] = make_uint2(h0, h1);
-    o[1] = make_uint2(m0, m1);
-    o[2] = make_uint2(l0, l1);
-}
 
 // image[ms][chunk][tap m][piece][lane] (16 B): row ci = ms*32 + (lane & 31); the lane's 8 contraction elements are half
 // hh = lane >> 5 of the chunk: element e -> channel chunk*(16/S) + e / (S/2), phase r = hh*S/2 + e % (S/2),

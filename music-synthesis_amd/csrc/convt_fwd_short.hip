@@ -11,43 +11,13 @@
 // into LDS (double-buffered, one barrier per chunk), the A fragments stream L2 -> registers a chunk ahead; split-K slices over
 // the input channels fill the chip, a finish kernel sums the slabs in slice order and applies bias + LeakyReLU.
 // Epilogue: a lane's low / high accumulators of one channel are output samples 2 q and 2 q + 1: 8-byte stores.
-#include "ms_common.h"
+#include "operand_split.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int XRS = 112;
 constexpr int PX_MAX = 350;
-constexpr unsigned OOB = 0xF0000000u;
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-__device__ __forceinline__ void split_quad(const float (&e)[4], uint2 (&o)[3]) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(e[0], e[1], h0, m0, l0);
-    split_pair(e[2], e[3], h1, m1, l1);
-    o[0] = make_uint2(h0, h1);
-    o[1] = make_uint2(m0, m1);
-    o[2] = make_uint2(l0, l1);
-}
 
 struct CsP {
     int B, Cin, Cout, L;      // batch rows, input channels (contraction), output channels, input positions per row (power of two)

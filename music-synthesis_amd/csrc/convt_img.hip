@@ -16,43 +16,15 @@
 // maximum of the NEXT window is published under the current tile, as in the atom kernel), the weights are packed as
 // pieces of S_w w (S_w: a power of two from the largest weight).  The short-row K-loop kernel (convt_fwd_short.hip) shares the pack kernel and keeps the exact
 // three-piece bf16 split (np = 3 images): agreement between the schemes ~3e-7.
-#include "ms_common.h"
+#include "operand_split.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int XRS = 80;                  // bytes per LDS column of a 16-channel chunk: 2 fp16 pieces x 32 + 16
-constexpr unsigned OOB = 0xF0000000u;
-// NP = 2: the weights are packed as the fp16 pieces of S_w w, S_w a power of two from the tensor's largest magnitude (it goes to
-// [2^12, 2^13): weights of any magnitude; see conv5_img.hip): partial maxima -> image tail -> the pack reduces them and leaves
-// 1 / S_w there for the kernel.
+// NP = 2: the weights are packed as the fp16 pieces of S_w w, S_w the weight_scale of the whole tensor (as conv5_img.hip):
+// partial maxima -> image tail -> the pack reduces them and leaves 1 / S_w there for the kernel.
 constexpr int W_NPART = 256;          // partial maxima of a weight tensor (one workgroup each)
-// (called by ALL 256 threads of a pack workgroup, before any of them returns: the first wave reduces the partials, LDS broadcasts)
-__device__ __forceinline__ void weight_scale(const float* __restrict__ pm, float& S, float& invS) {
-    __shared__ float wmax_s;
-    if (threadIdx.x < 64) {
-        float m = fmaxf(fmaxf(pm[threadIdx.x], pm[threadIdx.x + 64]), fmaxf(pm[threadIdx.x + 128], pm[threadIdx.x + 192]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (threadIdx.x == 0) wmax_s = m;
-    }
-    __syncthreads();
-    const float m = wmax_s;
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (266u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 12u) << 23) : 1.f;
-}
 // end of the NP = 2 data of an image (the allocation is sized for three pieces), in 16-byte units
 __host__ __device__ inline size_t ct_tail_u4(int Cin, int Cout, int S) { return (size_t)(Cout * S / 32) * (Cin / 16) * 2 * 2 * 64; }
 
@@ -61,55 +33,17 @@ __global__ __launch_bounds__(256) void k_convt_wmax(const float* __restrict__ W,
     const size_t per = (n + W_NPART - 1) / W_NPART, lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
     float m = 0.f;
     // 16 bytes per lane at any 4-byte aligned address (a view into a flat parameter bucket): a 21 MB tensor in ~7 us, not 21
-    typedef float f32x4w __attribute__((ext_vector_type(4), aligned(4)));
     size_t i = lo + 4 * (size_t)threadIdx.x;
     for (; i + 3 < hi; i += 1024) {
-        const f32x4w v = *reinterpret_cast<const f32x4w*>(W + i);
+        const f32x4u v = *reinterpret_cast<const f32x4u*>(W + i);
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (; i < hi; ++i) m = fmaxf(m, fabsf(W[i]));                     // (the one thread whose quad crosses the part's end)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));        // (not wave_max: see k_conv5_wmax)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) pm[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-// (a, b), scaled into fp16's range by the caller -> a = h.lo + l.lo to 22 significand bits (atom_fused.hip)
-__device__ __forceinline__ void split_pair2(float a, float b, unsigned& h, unsigned& l) {
-    const f32x2 v = {a, b};
-    const f16x2 hi = __builtin_convertvector(v, f16x2);
-    const f16x2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), f16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-__device__ __forceinline__ void block_scale(float m, float& S, float& invS) {
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (268u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 14u) << 23) : 1.f;
-}
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-__device__ __forceinline__ void split_quad(const float (&e)[4], uint2 (&o)[3]) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(e[0], e[1], h0, m0, l0);
-    split_pair(e[2], e[3], h1, m1, l1);
-    o[0] = make_uint2(h0, h1);
-    o[1] = make_uint2(m0, m1);
-    o[2] = make_uint2(l0, l1);
 }
 
 // image[cg][half][chunk][tap jj][piece][lane] (16 B): sub-tile (cg, half) row i = lane & 31 is
@@ -124,7 +58,7 @@ __global__ __launch_bounds__(256) void k_convt_pack(const float* __restrict__ W,
     float WS = 1.f, iWS = 1.f;
     if (np == 2) {
         float* tail = reinterpret_cast<float*>(img + ct_tail_u4(Cin, Cout, S));
-        weight_scale(tail, WS, iWS);
+        weight_scale(weight_max256(tail), WS, iWS);
         if (idx == 0) tail[W_NPART] = iWS;
     }
     if (idx >= total) return;
@@ -146,7 +80,7 @@ __global__ __launch_bounds__(256) void k_convt_pack(const float* __restrict__ W,
         const float a = W[((size_t)(ci0 + 2 * q) * Cout + co) * K + k];
         const float b = W[((size_t)(ci0 + 2 * q + 1) * Cout + co) * K + k];
         if (np == 3) split_pair(a, b, pc[0][q], pc[1][q], pc[2][q]);
-        else { split_pair2(a * WS, b * WS, pc[0][q], pc[1][q]); pc[2][q] = 0u; }
+        else { split_pair(a * WS, b * WS, pc[0][q], pc[1][q]); pc[2][q] = 0u; }
     }
     u32x4* dst = img + ((size_t)((((cg * 2 + half) * NC + chunk) * 2 + jj) * np)) * 64 + lane;
     for (int pp = 0; pp < np; ++pp) dst[pp * 64] = u32x4{pc[pp][0], pc[pp][1], pc[pp][2], pc[pp][3]};
@@ -225,8 +159,7 @@ __global__ __launch_bounds__(256, 1) void k_convt_img(CtP p, const float* __rest
             for (int cc = 0; cc < 4; ++cc)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(rx[r][cc][e]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        m = wave_max(m);
         if (lane == 0) smax[wid] = m;
     };
     auto store_x = [&](float SC_) {
@@ -237,8 +170,8 @@ __global__ __launch_bounds__(256, 1) void k_convt_img(CtP p, const float* __rest
                 const int i = u_lcol[r] + e;
                 if (i < 0 || i >= NXA) continue;
                 unsigned h0, l0, h1, l1;
-                split_pair2(rx[r][0][e] * SC_, rx[r][1][e] * SC_, h0, l0);
-                split_pair2(rx[r][2][e] * SC_, rx[r][3][e] * SC_, h1, l1);
+                split_pair(rx[r][0][e] * SC_, rx[r][1][e] * SC_, h0, l0);
+                split_pair(rx[r][2][e] * SC_, rx[r][3][e] * SC_, h1, l1);
                 unsigned char* dst = smem_ct + u_lbase[r] + i * XRS;
                 *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
                 *reinterpret_cast<uint2*>(dst + 32) = make_uint2(l0, l1);

@@ -9,17 +9,13 @@
 //
 // Arithmetic is plain fp32 FMA in a fixed order: results are deterministic; they differ from the per-scale kernels only by
 // summation order (tests/test_gpu_parts.py: float64 reference 1e-6, per-scale launches 1e-6).
-#include "ms_common.h"
+#include "operand_split.h"
 #include "gconv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
-constexpr unsigned OOB = 0xF0000000u;
 constexpr int NP = MS_CONV_PARTS_MAX;
 
 // Table of parts.  wg0[i]: first workgroup of part i (a prefix sum; wg0[count] = grid size).
@@ -50,17 +46,6 @@ __device__ __forceinline__ DPart pick_part(const DParts& q, int wg) {
 }
 
 __device__ __forceinline__ float lrelu_grad(float g, float y, float slope) { return y > 0.f ? g : g * slope; }
-
-// 4 consecutive samples t .. t+3 of the row that starts at element `row_elems` (length L) of a tensor read through rs: one
-// (possibly unaligned) 16-byte load; samples outside [0, L) read 0.0.  t must be a multiple of 4: the vector then lies wholly
-// in front of the row or starts inside it, and only the one across the row END needs clearing.
-__device__ __forceinline__ f32x4 load_row4(__amdgpu_buffer_rsrc_t rs, unsigned row_elems, int t, int L) {
-    const bool any = t >= 0 && t < L;
-    f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, any ? (row_elems + (unsigned)t) * 4u : OOB, 0, 0));
-#pragma unroll
-    for (int e = 1; e < 4; ++e) v[e] = t + e < L ? v[e] : 0.f;
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------ first conv, forward
 // y[b, co, t] = lrelu(bias[co] + sum_k w[co, k] x[b, 0, t + k - 7]).  A workgroup owns 1024 samples of one (part, batch row):

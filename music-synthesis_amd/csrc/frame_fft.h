@@ -69,6 +69,23 @@ __device__ __forceinline__ void ms_frame_ifft_bitrev(int n_fft, float* re, float
     }
 }
 
+// ... and the end of both backward frame kernels: gf[n] = window[n] * u[n], u read from its bit-reversed slot in re
+__device__ __forceinline__ void ms_frame_store_bitrev(const float* __restrict__ window, const float* re, int n_fft, int log2n,
+                                                      float* __restrict__ gf) {
+    for (int n = threadIdx.x; n < n_fft; n += 256)
+        gf[n] = window[n] * re[(int)(__brev((unsigned)n) >> (32 - log2n))];
+}
+
+// The gather step of both backward passes: the sum of g[f][q - f*hop] over the frames f that cover position q
+// (q - f*hop in [0, n_fft)), in increasing f
+__device__ __forceinline__ float ms_frames_over(const float* __restrict__ g, int q, int n_fft, int hop, int frames) {
+    const int f_lo = q < n_fft ? 0 : (q - n_fft) / hop + 1;
+    const int f_hi = min(frames - 1, q / hop);
+    float acc = 0.f;
+    for (int f = f_lo; f <= f_hi; ++f) acc += g[(size_t)f * n_fft + (q - f * hop)];
+    return acc;
+}
+
 // log2(n_fft), or -1 when n_fft is not a power of two in [64, 4096]
 static inline int ms_frame_log2(int n_fft) {
     int log2n = 0;

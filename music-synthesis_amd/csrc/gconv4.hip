@@ -17,7 +17,7 @@
 //     samples, so D[co] of lane (quad, j) IS gw[co][ci][4 quad + j] -- no cross-lane reduction, no slabs, no finish launch,
 //     a fixed summation order.  Rows travel global -> registers -> LDS one chunk ahead of the arithmetic.
 // 656 FMAs per item either way: 0.62 GMAC per pass at B = 64 x 3 scales = 16 us of the vector pipe at full rate.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "gconv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -25,11 +25,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr unsigned OOB = 0xF0000000u;
 constexpr int NP = MS_CONV_PARTS_MAX;
 constexpr int K4 = 41, PAD4 = 20, CG = 4, WPG = CG * CG * K4;      // 656 weights per group, [co][ci][k]
 constexpr int NMIN = 8, NMAX = 64;                                 // outputs per row the kernels take (Lin 29 .. 256)
@@ -61,16 +56,6 @@ __device__ __forceinline__ G4Part pick_part(const G4Parts& q, int wg) {
     for (int k = 1; k < NP; ++k)
         if (k < q.count && wg >= q.wg0[k]) p = G4Part{q.B[k], q.L[k], q.n[k], wg - q.wg0[k], q.a[k], q.b[k], q.c[k], q.o[k]};
     return p;
-}
-
-// 4 consecutive samples t .. t+3 of the row at element `row_elems` (length L): one 16-byte load at any 4-byte aligned
-// address; samples outside [0, L) read 0.0.  t is a multiple of 4 (disc_parts.hip).
-__device__ __forceinline__ f32x4 load_row4(__amdgpu_buffer_rsrc_t rs, unsigned row_elems, int t, int L) {
-    const bool any = t >= 0 && t < L;
-    f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, any ? (row_elems + (unsigned)t) * 4u : OOB, 0, 0));
-#pragma unroll
-    for (int e = 1; e < 4; ++e) v[e] = t + e < L ? v[e] : 0.f;
-    return v;
 }
 
 extern __shared__ __attribute__((aligned(16))) float g4_smem[];

@@ -7,14 +7,12 @@
 // group in registers and sweeps 16-output time tiles; the input rows are staged in LDS once per
 // workgroup in a phase-split layout ([ci][u mod stride][u / stride]) so that the stride-4 gather
 // of tap j becomes a unit-stride, conflict-free ds_read for every lane.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "gconv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GK = 41, GS = 4, GCG = 4;      // taps, stride, input channels per group
 

@@ -18,45 +18,16 @@
 // modulo the 32-quad bank window: conflict-free for ds_read_b64.
 // Short rows (the coarse scales: Lout = 9 .. 65) are covered by RB = 2 / 4 segments of 32 / 16 outputs
 // per unit, taken from consecutive (batch row, segment) pairs.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "gconv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // a 16-byte access at any 4-byte aligned address
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int GK = 41, GS = 4, GCG = 4;
-// The weights of a wave's group are split in registers under the wave's own power-of-two scale S_w (their largest magnitude goes to
-// [2^12, 2^13): weights of any magnitude; r04 took the pieces of 64 w and overflowed to inf from |w| >= 2^9).
-
-// Block-scaled two-piece fp16 split (r04, atom_fused.hip): (a, b) scaled into fp16's range by the caller ->
-// a = h.lo + l.lo to 22 significand bits (block maximum in [2^8, 2^15)); products h h' + h l' + l h' into one fp32
-// accumulator: three MFMAs instead of six.
-__device__ __forceinline__ void split_pair2(float a, float b, unsigned& h, unsigned& l) {
-    const f32x2 v = {a, b};
-    const f16x2 hi = __builtin_convertvector(v, f16x2);
-    const f16x2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), f16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-// S = 2^k with m S in [2^14, 2^15), and 1 / S (exact powers of two); 1 for a zero / denormal-range / non-finite maximum
-__device__ __forceinline__ void block_scale(float m, float& S, float& invS) {
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (268u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 14u) << 23) : 1.f;
-}
+// NP = 2 blocks: the weights of a wave's group are split in registers under the wave's own weight_scale, the activations of a
+// unit under the wave's block_scale (operand_split.h).
 
 // largest value over the wave, wave-uniform: 16 lanes by DPP (quad swaps, half-row mirror, row mirror), the four rows by readlane
 __device__ __forceinline__ float wave_max_dpp(float m) {
@@ -70,27 +41,6 @@ __device__ __forceinline__ float wave_max_dpp(float m) {
     return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 constexpr int NG = 6;                         // tap groups of 8
-
-// S = 2^k with m S in [2^12, 2^13), and 1 / S; 1 for a zero / denormal-range / non-finite maximum
-__device__ __forceinline__ void weight_scale(float m, float& S, float& invS) {
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (266u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 12u) << 23) : 1.f;
-}
-
-// (a, b) -> three packed bf16 pairs with a = h.lo + m.lo + l.lo exactly (same for b in the high halves)
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
 
 template <int RB>
 struct GF {
@@ -164,7 +114,6 @@ __device__ __forceinline__ void gconv_fwd_body(const ConvP& p, int spr, int nseg
 
     // Inputs are read through a buffer descriptor: a quad that lies outside its row (the zero padding) or
     // behind the last segment carries an out-of-range offset and the hardware range check returns 0.0f.
-    constexpr unsigned OOB = 0xF0000000u;
     // (true size: the unaligned quad across the END of the tensor's last row must not touch memory behind the tensor -- the
     //  range check returns 0.0 for those dwords)
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, 4u * (unsigned)(p.B * p.Cin * p.Lin), 0x00020000);
@@ -209,8 +158,8 @@ __device__ __forceinline__ void gconv_fwd_body(const ConvP& p, int spr, int nseg
     // registers -> LDS: scaled by the unit's power-of-two block scale, split into two fp16 pieces, one 8-byte quad per piece
     auto stage_item = [&](const f32x4& v, int lds_off, float S) {
         unsigned h0, l0, h1, l1;
-        split_pair2(v[0] * S, v[1] * S, h0, l0);
-        split_pair2(v[2] * S, v[3] * S, h1, l1);
+        split_pair(v[0] * S, v[1] * S, h0, l0);
+        split_pair(v[2] * S, v[3] * S, h1, l1);
         unsigned char* d = lds + wv_off + lds_off;
         *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
         *reinterpret_cast<uint2*>(d + C::PIECE_BYTES) = make_uint2(l0, l1);
@@ -245,7 +194,7 @@ __device__ __forceinline__ void gconv_fwd_body(const ConvP& p, int spr, int nseg
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 unsigned hh, ll;
-                split_pair2(wv[8 * G + 2 * q], wv[8 * G + 2 * q + 1], hh, ll);
+                split_pair(wv[8 * G + 2 * q], wv[8 * G + 2 * q + 1], hh, ll);
                 h[q] = hh; l[q] = ll;
             }
             A[G][0] = __builtin_bit_cast(f16x8, h);
@@ -477,7 +426,6 @@ __device__ __forceinline__ void gconv_wgrad_body(const ConvP& p, const float* __
         x_lds[i] = act ? ci * WXROW + Q * 8 : 3 * WXROW + WXQ * 8;        // spare quad behind the last row's data
         x_c[i] = act ? (unsigned)(ci * p.Lin + 4 * Q) : 0x3C000000u;      // (elements; x4 = out of range)
     }
-    constexpr unsigned OOB = 0xF0000000u;
     // (true sizes: see the forward kernel)
     const unsigned g_bytes = 4u * (unsigned)(p.B * p.Cout * p.Lout);
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, 4u * (unsigned)(p.B * p.Cin * p.Lin), 0x00020000);
@@ -615,8 +563,8 @@ __device__ __forceinline__ void gconv_wgrad_body(const ConvP& p, const float* __
             for (int k = 0; k < 4; ++k) e[k] = ms_act_grad(gv[i][k], ga[i][k], kind, p.slope);
             bsum[i] += (e[0] + e[1]) + (e[2] + e[3]);
             unsigned h0, l0, h1, l1;
-            split_pair2(e[0] * Sg, e[1] * Sg, h0, l0);
-            split_pair2(e[2] * Sg, e[3] * Sg, h1, l1);
+            split_pair(e[0] * Sg, e[1] * Sg, h0, l0);
+            split_pair(e[2] * Sg, e[3] * Sg, h1, l1);
             unsigned char* d = gimg + (g_tb * 16 + ((co0 + 4 * i) ^ g_tb)) * 16 + (tq & 1) * 8;
             *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(d + WG_PIECE) = make_uint2(l0, l1);
@@ -624,8 +572,8 @@ __device__ __forceinline__ void gconv_wgrad_body(const ConvP& p, const float* __
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             unsigned h0, l0, h1, l1;
-            split_pair2(xv[i][0] * Sx, xv[i][1] * Sx, h0, l0);
-            split_pair2(xv[i][2] * Sx, xv[i][3] * Sx, h1, l1);
+            split_pair(xv[i][0] * Sx, xv[i][1] * Sx, h0, l0);
+            split_pair(xv[i][2] * Sx, xv[i][3] * Sx, h1, l1);
             unsigned char* d = ximg + x_lds[i];
             *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(d + WX_PIECE) = make_uint2(l0, l1);
@@ -809,7 +757,6 @@ __device__ __forceinline__ void gconv_bwd_data_body(const ConvP& p, int tiles, i
     // staging item of this lane: co quad cq, position quad pq
     const int cq = lane & 3, pq = lane >> 2;
     unsigned char* wr = img + (cq >> 1) * BOCT + (4 * pq) * 16 + (cq & 1) * 8;       // + j * 16 (position), + piece
-    constexpr unsigned OOB = 0xF0000000u;
     const unsigned g_bytes = 4u * (unsigned)(p.B * p.Cout * p.Lout);            // (true sizes: see the forward kernel)
     const auto rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gy), 0, g_bytes, 0x00020000);
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(y_act ? y_act : gy), 0, g_bytes, 0x00020000);
@@ -878,7 +825,7 @@ __device__ __forceinline__ void gconv_bwd_data_body(const ConvP& p, int tiles, i
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 unsigned hh, ll;
-                split_pair2(wall[J][2 * q] * WS, wall[J][2 * q + 1] * WS, hh, ll);
+                split_pair(wall[J][2 * q] * WS, wall[J][2 * q + 1] * WS, hh, ll);
                 h[q] = hh; l[q] = ll;
             }
             A[J][0] = __builtin_bit_cast(f16x8, h);
@@ -905,8 +852,8 @@ __device__ __forceinline__ void gconv_bwd_data_body(const ConvP& p, int tiles, i
 #pragma unroll
             for (int k = 0; k < 4; ++k) e[k] = ms_act_grad(gv[k][j], ga[k][j], kind, p.slope) * S;
             unsigned h0, l0, h1, l1;
-            split_pair2(e[0], e[1], h0, l0);
-            split_pair2(e[2], e[3], h1, l1);
+            split_pair(e[0], e[1], h0, l0);
+            split_pair(e[2], e[3], h1, l1);
             *reinterpret_cast<uint2*>(wr + j * 16) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(wr + j * 16 + B_PIECE) = make_uint2(l0, l1);
         }

@@ -8,11 +8,9 @@
 //   interleave  out[(b, q)][phase][n] = y[phase][(b, q)][n]      (the phases' output rows into image order)
 //   split       the inverse (backward of interleave)
 // 16-byte vectors throughout (C*W % 4 == 0), grid-stride, one line block (C*W floats) is contiguous on both sides.
-#include "ms_common.h"
+#include "operand_split.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct LinesP {
     int B, H, nph, nt;

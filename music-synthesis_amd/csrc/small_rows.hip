@@ -22,13 +22,11 @@
 // k_conv_small<K>    Conv1d, stride 1, dilation 1, one group, zero or reflection padding, tiles of 32 output positions:
 //     thread = (half of the input channels, output channel of 4, position of 32); window and weights from LDS; 128 workgroups
 //     x 9 KB of weights for the 80 -> 512 layer.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "conv_thin.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct CtsP {
     int B, Cin, Cout, Lin, Lout;

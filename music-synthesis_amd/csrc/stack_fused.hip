@@ -55,7 +55,6 @@ __global__ __launch_bounds__(64 * NW, C >= 128 ? 1 : 2) void k_stack_fwd(StackP 
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid / WGN, wn = wid % WGN;
     const int L = p.L;
-    constexpr unsigned OOB = 0xF0000000u;
     const int ntiles = p.B * p.tiles_per_row;
 
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, 0x80000000u, 0x00020000);

@@ -90,18 +90,7 @@ __global__ __launch_bounds__(256) void k_stft_mag_bwd_frame(const float* __restr
     }
     __syncthreads();
     ms_frame_ifft_bitrev(n_fft, fre, fim);
-    float* gf = gframes + ((size_t)b * frames + fr) * n_fft;
-    for (int n = threadIdx.x; n < n_fft; n += 256)
-        gf[n] = window[n] * fre[(int)(__brev((unsigned)n) >> (32 - log2n))];
-}
-
-// sum over the frames f that cover padded position q (q - f*hop in [0, n_fft)), in increasing f
-__device__ __forceinline__ float stft_frames_over(const float* __restrict__ g, int q, int n_fft, int hop, int frames) {
-    const int f_lo = q < n_fft ? 0 : (q - n_fft) / hop + 1;
-    const int f_hi = min(frames - 1, q / hop);
-    float acc = 0.f;
-    for (int f = f_lo; f <= f_hi; ++f) acc += g[(size_t)f * n_fft + (q - f * hop)];
-    return acc;
+    ms_frame_store_bitrev(window, fre, n_fft, log2n, gframes + ((size_t)b * frames + fr) * n_fft);
 }
 
 // grad_audio[b][s]: sample s sits at padded position p + s; the left pad position p - s (1 <= s <= p) and the right
@@ -112,9 +101,9 @@ __global__ __launch_bounds__(256) void k_stft_mag_bwd_gather(const float* __rest
     if (s >= N) return;
     const int p = n_fft >> 1;
     const float* g = gframes + (size_t)b * frames * n_fft;
-    float acc = stft_frames_over(g, p + s, n_fft, hop, frames);
-    if (s >= 1 && s <= p) acc += stft_frames_over(g, p - s, n_fft, hop, frames);
-    if (s >= N - 1 - p && s <= N - 2) acc += stft_frames_over(g, p + 2 * (N - 1) - s, n_fft, hop, frames);
+    float acc = ms_frames_over(g, p + s, n_fft, hop, frames);
+    if (s >= 1 && s <= p) acc += ms_frames_over(g, p - s, n_fft, hop, frames);
+    if (s >= N - 1 - p && s <= N - 2) acc += ms_frames_over(g, p + 2 * (N - 1) - s, n_fft, hop, frames);
     grad_audio[(size_t)b * N + s] = acc;
 }
 

@@ -15,33 +15,15 @@
 // `nsplit` slabs (deterministic reduce: msm_wgrad_reduce).  Staging as in wgrad_k5.hip: global loads of step s+1 in
 // flight during the MFMAs of step s, two LDS images, one barrier per step.  The LeakyReLU in front of the transposed
 // conv (in_act) is applied to x on its way into LDS.  The bias gradient is a separate channel sum (api.hip).
-#include "ms_common.h"
+#include "operand_split.h"
 #include "conv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
 
 struct W8P {
     int B, CI, CO, L, spr, nsteps, sps, act, in_act;      // spr = L / 32 steps per batch row
@@ -71,7 +53,6 @@ __global__ __launch_bounds__(NT) void k_wgrad_convt8_split(W8P p, const float* _
     const int kind = y_act ? p.act : MS_ACT_NONE;
     const int r64 = tid % TCI, oc = tid / TCI;            // input item: channel r64 of octet slot oc
     const int Lg = p.L * TS;
-    constexpr unsigned OOB = 0xF0000000u;
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, 0x80000000u, 0x00020000);
     const auto rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gy), 0, 0x80000000u, 0x00020000);
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(y_act ? y_act : gy), 0, 0x80000000u, 0x00020000);

@@ -13,42 +13,15 @@
 // with zeros at the row ends), splits and stores 8-byte groups; the next step's global loads are in flight during the MFMAs;
 // split-K over batch rows fills the chip, slabs are summed in slice order (msm_wgrad_reduce, deterministic).
 // Arithmetic: exact 3-piece bf16 split, six products per multiply, fp32 accumulation.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "conv_mfma.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BM = 128, BN = 128, BK = 32;      // output tile, positions per step
 constexpr int RS = 208;                          // LDS bytes per tile row: 3 pieces x 64 + 16
 constexpr int NT = 512;
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-__device__ __forceinline__ void split_quad(const float (&e)[4], uint2 (&o)[3]) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(e[0], e[1], h0, m0, l0);
-    split_pair(e[2], e[3], h1, m1, l1);
-    o[0] = make_uint2(h0, h1);
-    o[1] = make_uint2(m0, m1);
-    o[2] = make_uint2(l0, l1);
-}
 
 struct W2P {
     int B, CI, CO, W;         // batch rows, input channels (GEMM rows), gradient channels (GEMM columns / 4), positions per row

@@ -16,31 +16,12 @@
 // across all steps; the batch is cut into `nsplit` slabs (deterministic reduce: msm_wgrad_reduce).  Staging: every
 // thread owns one (co, octet) and one (ci, octet) item per step -- global loads of step s+1 are in flight during the
 // MFMAs of step s, two LDS images, one barrier per step.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "conv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hi = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hi, f32x2);
-    const bf16x2 mi = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mi, f32x2);
-    const bf16x2 lo = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
 
 // The contraction runs over OCTETS of 8 consecutive outputs.  The octets of up to MS_CONV_PARTS_MAX inputs ("parts": the
 // shared discriminator's three scales, reference discriminator/melgan.py:13-27) form one index space -- part i owns octets
@@ -74,7 +55,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_k5_split(W5P p, float* __restr
     const int m0 = blockIdx.x * TCO, c0 = blockIdx.y * TCI, z = blockIdx.z;
     const int kind = p.ya[0] ? p.act : MS_ACT_NONE;
     const int r64 = tid & 63, oc = __builtin_amdgcn_readfirstlane(tid >> 6);   // staging item: row (co / ci) r64 of octet slot oc
-    constexpr unsigned OOB = 0xF0000000u;
 
     float gv[8], ga[8], xv[12];
     auto gload = [&](int step) {
@@ -290,16 +270,6 @@ __device__ __forceinline__ W5Part w5_part(const W5Q& q, int key, bool by_octet) 
     return p;
 }
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// S = 2^k with m S in [2^12, 2^13) (room for the pieces of every batch row), and 1 / S; 1 for zero / non-finite maxima
-__device__ __forceinline__ void chunk_scale(float m, float& S, float& invS) {
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (266u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 12u) << 23) : 1.f;
-}
 
 // Pre-pass workgroups = (row of a part, block of 128 channels); blocks [0, C / 128) belong to the input, the rest to the gradient.
 constexpr int WB_CH = 128;
@@ -360,7 +330,7 @@ __global__ __launch_bounds__(256) void k_w5_split(W5Q q, const float* __restrict
             const int cl = i / NOP, oc = i - cl * NOP, co = blk * WB_CH + cl;
             const bool live = oc < NO;
             float S, invS;
-            chunk_scale(cm[cl >> 4], S, invS);
+            weight_scale(cm[cl >> 4], S, invS);         // (top 12, not 14: room for the pieces of every batch row)
             unsigned hh[4], ll[4];
             float sum = 0.f;
 #pragma unroll
@@ -375,10 +345,7 @@ __global__ __launch_bounds__(256) void k_w5_split(W5Q q, const float* __restrict
                     e[j] = v;
                     sum += v;
                 }
-                const f32x2 s2 = {e[0] * S, e[1] * S};
-                const f16x2 hi = __builtin_convertvector(s2, f16x2);
-                const f16x2 lo = __builtin_convertvector(s2 - __builtin_convertvector(hi, f32x2), f16x2);
-                hh[k] = __builtin_bit_cast(unsigned, hi); ll[k] = __builtin_bit_cast(unsigned, lo);
+                split_pair(e[0] * S, e[1] * S, hh[k], ll[k]);
             }
             if (live) {
                 const size_t o = ((size_t)b * q.M + co) * (8 * NO) + 8 * oc;
@@ -396,7 +363,7 @@ __global__ __launch_bounds__(256) void k_w5_split(W5Q q, const float* __restrict
     for (int i = tid; i < WB_CH * NV; i += 256) {
         const int cl = i / NV, j = i - cl * NV, ci = blk * WB_CH + cl;
         float S, invS;
-        chunk_scale(cm[cl >> 4], S, invS);
+        weight_scale(cm[cl >> 4], S, invS);
         unsigned hh[4], ll[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -406,10 +373,7 @@ __global__ __launch_bounds__(256) void k_w5_split(W5Q q, const float* __restrict
                 const int t = 8 * j - 2 + 2 * k + jj;
                 e[jj] = (t >= 0 && t < L) ? xr[(size_t)cl * L + t] : 0.f;
             }
-            const f32x2 s2 = {e[0] * S, e[1] * S};
-            const f16x2 hi = __builtin_convertvector(s2, f16x2);
-            const f16x2 lo = __builtin_convertvector(s2 - __builtin_convertvector(hi, f32x2), f16x2);
-            hh[k] = __builtin_bit_cast(unsigned, hi); ll[k] = __builtin_bit_cast(unsigned, lo);
+            split_pair(e[0] * S, e[1] * S, hh[k], ll[k]);
         }
         const size_t o = ((size_t)b * q.C + ci) * (8 * NO + 8) + 8 * j;
         *reinterpret_cast<u32x4*>(p.xh + o) = (u32x4){hh[0], hh[1], hh[2], hh[3]};
@@ -529,11 +493,11 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_k5_pre(W5Q p, float* __restric
     // ---- undo the chunk scales: an m-tile of 16 co is one gradient chunk, a wave's 16 ci one input chunk
     const int ncx = p.C / 16;
     float sx, isx;
-    chunk_scale(__builtin_bit_cast(float, p.mx[c0 / 16 + wid]), sx, isx);
+    weight_scale(__builtin_bit_cast(float, p.mx[c0 / 16 + wid]), sx, isx);
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
         float sg, isg;
-        chunk_scale(__builtin_bit_cast(float, p.mx[ncx + m0 / 16 + mt]), sg, isg);
+        weight_scale(__builtin_bit_cast(float, p.mx[ncx + m0 / 16 + mt]), sg, isg);
         const float f = isx * isg;
 #pragma unroll
         for (int k = 0; k < 5; ++k) acc[mt][k] *= f;

@@ -14,15 +14,13 @@
 // runs over the padded columns.
 //
 // Split-K over chunks (grid.z) into per-slice slabs, summed in slice order by k_wgrad_reduce.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "conv_mfma.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CB = 64;          // input channels per workgroup
 constexpr int KMAX = 64;        // contraction columns per chunk
@@ -412,32 +410,6 @@ __global__ __launch_bounds__(256) void k_wgrad_rows(WrP p, const float* __restri
 // matrix pipe and the vector work of the staging slot by slot (as k_conv_rows3p), each with its own
 // single-buffered LDS tiles; at the end group 1's accumulators are added to group 0's through LDS and
 // the tile goes to the split-K slab in the layout of k_wgrad_rows (same reduce kernels).
-typedef __bf16 w3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 w3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float w3_f32x2 __attribute__((ext_vector_type(2)));
-typedef float w3_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void w3_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    const w3_f32x2 v = {a, b};
-    const w3_bf16x2 hi = __builtin_convertvector(v, w3_bf16x2);
-    const w3_f32x2 r1 = v - __builtin_convertvector(hi, w3_f32x2);
-    const w3_bf16x2 mi = __builtin_convertvector(r1, w3_bf16x2);
-    const w3_f32x2 r2 = r1 - __builtin_convertvector(mi, w3_f32x2);
-    const w3_bf16x2 lo = __builtin_convertvector(r2, w3_bf16x2);
-    h = __builtin_bit_cast(unsigned, hi);
-    m = __builtin_bit_cast(unsigned, mi);
-    l = __builtin_bit_cast(unsigned, lo);
-}
-
-// 4 consecutive samples -> one 8-byte group per piece
-__device__ __forceinline__ void w3_split_quad(const float (&e)[4], uint2 (&o)[3]) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    w3_split_pair(e[0], e[1], h0, m0, l0);
-    w3_split_pair(e[2], e[3], h1, m1, l1);
-    o[0] = make_uint2(h0, h1);
-    o[1] = make_uint2(m0, m1);
-    o[2] = make_uint2(l0, l1);
-}
 
 // the 8 16-bit elements that start E elements into the 16 elements of (lo, hi)
 template <int E>
@@ -458,29 +430,21 @@ __device__ __forceinline__ uint4 w3_funnel(const uint4& lo, const uint4& hi) {
 // r04: the same kernel on block-scaled two-piece fp16 operands (NP = 2, three products per multiply into one fp32
 // accumulator: atom_fused.hip) when the caller hands in upper bounds of both tensors' magnitudes (the fused atom kernels
 // publish them): one power-of-two scale per tensor puts its largest magnitude at 2^14, the slab is written unscaled.
-typedef _Float16 w3_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 w3_f16x8 __attribute__((ext_vector_type(8)));
-
+// The quad split of k_wgrad_rows3.  NP = 2 is spelled out here in this kernel's own order -- both high pieces, then both low
+// pieces -- where operand_split.h's split_quad<2> finishes one pair before the other: the same values, but the SOLO
+// instantiations come out of the scheduler in another instruction order, and that would want a measurement.
 template <int NP>
-__device__ __forceinline__ void w3_split_quad_np(const float (&e)[4], uint2 (&o)[NP]) {
+__device__ __forceinline__ void w3_split_quad(const float (&e)[4], uint2 (&o)[NP]) {
     if constexpr (NP == 3) {
-        w3_split_quad(e, o);
+        split_quad<3>(e, o);
     } else {
-        const w3_f32x2 v0 = {e[0], e[1]}, v1 = {e[2], e[3]};
-        const w3_f16x2 h0 = __builtin_convertvector(v0, w3_f16x2), h1 = __builtin_convertvector(v1, w3_f16x2);
-        const w3_f16x2 l0 = __builtin_convertvector(v0 - __builtin_convertvector(h0, w3_f32x2), w3_f16x2);
-        const w3_f16x2 l1 = __builtin_convertvector(v1 - __builtin_convertvector(h1, w3_f32x2), w3_f16x2);
+        const f32x2 v0 = {e[0], e[1]}, v1 = {e[2], e[3]};
+        const f16x2 h0 = __builtin_convertvector(v0, f16x2), h1 = __builtin_convertvector(v1, f16x2);
+        const f16x2 l0 = __builtin_convertvector(v0 - __builtin_convertvector(h0, f32x2), f16x2);
+        const f16x2 l1 = __builtin_convertvector(v1 - __builtin_convertvector(h1, f32x2), f16x2);
         o[0] = make_uint2(__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1));
         o[1] = make_uint2(__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1));
     }
-}
-
-// S = 2^k with m S in [2^14, 2^15) and 1 / S; 1 for a zero / denormal-range / non-finite bound (atom_fused.hip)
-__device__ __forceinline__ void w3_block_scale(float m, float& S, float& invS) {
-    const unsigned eb = (__builtin_bit_cast(unsigned, m) >> 23) & 0xFFu;
-    const bool ok = eb >= 16u && eb <= 250u;
-    S = ok ? __builtin_bit_cast(float, (268u - eb) << 23) : 1.f;
-    invS = ok ? __builtin_bit_cast(float, (eb - 14u) << 23) : 1.f;
 }
 
 template <int NP> constexpr int w3_grs() { return NP * 64 + 16; }      // bytes per gradient row: NP pieces x 32 samples x 2 + 16
@@ -548,7 +512,6 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
     const int NG = p.CK * K;
     const int PADA = (p.pad + 3) & ~3;               // halo in front of the row tile, rounded to whole vectors
 
-    constexpr unsigned OOB = 0xF0000000u;
     const auto rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G), 0, 0x80000000u, 0x00020000);
     const auto rsGa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Gact), 0, 0x80000000u, 0x00020000);
     const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, 0x80000000u, 0x00020000);
@@ -574,8 +537,8 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
 #pragma unroll
         for (int w = 1; w < (SOLO ? 4 : 8); ++w) { mx = fmaxf(mx, red[w]); mg = fmaxf(mg, red[8 + w]); }
         float ix, ig;
-        w3_block_scale(mx, Sx, ix);
-        w3_block_scale(mg, Sg, ig);
+        block_scale(mx, Sx, ix);
+        block_scale(mg, Sg, ig);
         kfin = ix * ig;
         __syncthreads();                             // (the staging buffers reuse this LDS)
     }
@@ -584,7 +547,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
     // vector gt & 15 of the 64-sample window that starts PADA samples in front of the tile)
     const int g_row = gt >> 3, g_t = 4 * (gt & 7);
     const int x_row = gt >> 4, x_u = 4 * (gt & 15);
-    w3_f32x4 gv[NGU], ga[GM ? 1 : NGU], xv[4];
+    f32x4 gv[NGU], ga[GM ? 1 : NGU], xv[4];
     uint2 gm[GM ? NGU : 1];                          // (GM) sign words of the vector's four columns
     // (GM) row g_row of every 32-row block: lane half (g_row >> 2) & 1, register (g_row & 3) + 4 (g_row >> 3)
     const int gm_h = (g_row >> 2) & 1, gm_sh = 15 - ((g_row & 3) + 4 * (g_row >> 3));
@@ -602,13 +565,13 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
         const unsigned mo = (live && tg < p.L) ? 2u * (unsigned)(((b * (p.M / 32) + m0 / 32) * 2 + gm_h) * p.L + tg) : OOB;
 #pragma unroll
         for (int q = 0; q < NGU; ++q) {
-            gv[q] = __builtin_bit_cast(w3_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsG, go, q * 32 * 4 * p.L, 0));
+            gv[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsG, go, q * 32 * 4 * p.L, 0));
             if constexpr (GM) gm[q] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rsGa, mo, q * 4 * p.L, 0));
-            else ga[q] = __builtin_bit_cast(w3_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsGa, go, q * 32 * 4 * p.L, 0));
+            else ga[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsGa, go, q * 32 * 4 * p.L, 0));
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            xv[q] = __builtin_bit_cast(w3_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, xo, q * 16 * 4 * p.L, 0));
+            xv[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, xo, q * 16 * 4 * p.L, 0));
     };
     auto stage = [&]() {
 #pragma unroll
@@ -631,7 +594,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
                 for (int i = 0; i < 4; ++i) e[i] *= Sg;
             }
             uint2 o3[NP];
-            w3_split_quad_np<NP>(e, o3);
+            w3_split_quad<NP>(e, o3);
             unsigned char* d = Gs + (g_row + 32 * q) * W3_GRS + g_t * 2;
 #pragma unroll
             for (int pp = 0; pp < NP; ++pp) *reinterpret_cast<uint2*>(d + pp * 64) = o3[pp];
@@ -644,7 +607,7 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
                 for (int i = 0; i < 4; ++i) e[i] *= Sx;
             }
             uint2 o3[NP];
-            w3_split_quad_np<NP>(e, o3);
+            w3_split_quad<NP>(e, o3);
             unsigned char* d = Xs + (x_row + 16 * q) * W3_XRS + x_u * 2;
 #pragma unroll
             for (int pp = 0; pp < NP; ++pp) *reinterpret_cast<uint2*>(d + pp * W3_XPB) = o3[pp];
@@ -714,11 +677,11 @@ __global__ __launch_bounds__(SOLO ? 256 : 512, SOLO ? 3 : 2) void k_wgrad_rows3(
 #pragma unroll
                     for (int i = 0; i < TM; ++i) {
                         if constexpr (NP == 3)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(w3_bf16x8, a[s][i][PAI[t]]),
-                                                                               __builtin_bit_cast(w3_bf16x8, b[PBI[t]]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s][i][PAI[t]]),
+                                                                               __builtin_bit_cast(bf16x8, b[PBI[t]]), acc[i][j], 0, 0, 0);
                         else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(w3_f16x8, a[s][i][PAI[t]]),
-                                                                              __builtin_bit_cast(w3_f16x8, b[PBI[t]]), acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[s][i][PAI[t]]),
+                                                                              __builtin_bit_cast(f16x8, b[PBI[t]]), acc[i][j], 0, 0, 0);
                     }
             }
         }

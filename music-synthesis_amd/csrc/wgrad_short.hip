@@ -13,16 +13,12 @@
 //   * the activation's derivative is applied to the gradient samples in registers; the bias gradient falls out of the same
 //     samples in the waves of the first input-channel tile;
 //   * loads of block i + 1 are issued before the 16 MFMAs of block i.
-#include "ms_common.h"
+#include "operand_split.h"
 #include "conv_mfma.h"
 #include <stdint.h>
 #include <stdlib.h>
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct WsP {
     int B, Cin, Cout, L, K, pad, Lq, act, reflect;

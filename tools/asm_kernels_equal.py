@@ -1,12 +1,14 @@
 """Are two device-only assembly files (hipcc --offload-arch=gfx950 --cuda-device-only -S) the same kernels?
 
 usage: python tools/asm_kernels_equal.py parent.s branch.s
+       python tools/asm_kernels_equal.py parent_dir branch_dir      (every x.s with kernels in parent_dir against branch_dir/x.s)
 
 A host-side refactor that touches no __global__ function may still change the ORDER in which templated kernels are
 instantiated, and with it the order of the functions in the .s file and the function index in every local label
 (.LBB<index>_<n>, .Lfunc_end<index>): a plain diff is then large although no instruction moved.  This compares the files
 function by function, by mangled name, with that index taken out of the labels; everything else must be identical,
 the kernel descriptors and metadata (compared as sorted blocks) included.  Exit status 0: same kernels."""
+import os
 import re
 import sys
 
@@ -39,4 +41,9 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    a, b = sys.argv[1:3]
+    if os.path.isdir(a):
+        names = [n for n in sorted(os.listdir(a)) if n.endswith(".s") and ".amdhsa_kernel" in open(os.path.join(a, n)).read()]
+        rcs = [print(n, end=": ") or main(os.path.join(a, n), os.path.join(b, n)) for n in names]      # (files without kernels: skipped)
+        sys.exit(1 if any(rcs) or not rcs else 0)
+    sys.exit(main(a, b))
