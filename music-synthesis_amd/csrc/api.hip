@@ -353,13 +353,19 @@ Plan convt_plan(const ms_convt1d_desc* d, const ConvP& p, int which) {
         if (mst_convt1_applicable(p)) return pl.add(TF_THIN, p);            // one output channel: a stream
         if (mss_convt_applicable(d)) pl.add(TF_LANES, p, 0, UNSUPPORTED);    // inference batch: a weight stream
         // (its epilogue stores 8 / 16 bytes at a time: an output at a 4-byte address goes to the direct kernel)
-        if (msm_convt_fwd_applicable(p)) pl.add(TF_MFMA, p, msm_convt_fwd_ws(p), UNSUPPORTED);
+        // (stride 4 ran without a workspace before its row-tile route existed: a call that brings none, or one off the 16-byte
+        //  grid, keeps the direct kernel instead of being refused)
+        if (msm_convt_fwd_applicable(p))
+            pl.add(TF_MFMA, p, msm_convt_fwd_ws(p), UNSUPPORTED | (p.stride == 4 ? SHORT_WS | ALIGNED_WS : 0u));
         ConvP q = p;     // direct path: the loader modifier kind rides in q.act, the epilogue gets p.act
         q.act = p.in_act ? MS_MOD_LRELU_FWD : MS_ACT_NONE;
         return pl.add(TF_DIRECT, q);
     }
     if (which == 1) {
-        if (msm_convt_bwd_applicable(p)) return pl.add(TD_MFMA, p, msm_convt_bwd_data_ws(p));
+        if (msm_convt_bwd_applicable(p)) {
+            if (p.stride != 4) return pl.add(TD_MFMA, p, msm_convt_bwd_data_ws(p));
+            pl.add(TD_MFMA, p, msm_convt_bwd_data_ws(p), SHORT_WS | ALIGNED_WS);      // (as the forward: see above)
+        }
         ConvP q = p;
         q.act = MS_ACT_NONE;
         if (msm_fwd_applicable(q)) {     // (this route's g.act is the kind of its activation OPERAND y_act: the conv has no epilogue)

@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma_rows(RowP p, const float* __r
         }
     } else {
         // transposed conv: GEMM row m' = co*S + r is output phase r of channel co; a lane's 4
-        // consecutive accumulator rows are 4 consecutive output samples (S = 8) or 2 x 2 (S = 2),
+        // consecutive accumulator rows are 4 consecutive output samples (S = 8, S = 4) or 2 x 2 (S = 2),
         // written as one 16-byte / two 8-byte stores along contiguous audio frames
         constexpr int ES = EPI_S > 0 ? EPI_S : 1;     // (EPI_S == 0 never reaches this branch)
         const int Cout = p.M / ES;
@@ -1445,10 +1445,12 @@ int launch_rows1(const RowPlan& pl, const RowOps& o, hipStream_t s, char* name) 
     MS_R1K(5, 16, 0, 1);
     MS_R1K(7, 4, 0, 1);
     MS_R1K(3, 8, 8, 1);      // transposed-conv forward: phase-interleaving epilogue
+    MS_R1K(3, 8, 4, 1);
     MS_R1K(3, 8, 2, 1);
 #undef MS_R1K
     if (K == 3 && CC == 8 && pl.epi_s == 0 && pl.has_act) {      // transposed-conv backward data: phase-split input rows
         if (pl.in_s == 8) return launch_rows1_k<3, 8, true, 0, 8>(pl, o, s, name);
+        if (pl.in_s == 4) return launch_rows1_k<3, 8, true, 0, 4>(pl, o, s, name);
         if (pl.in_s == 2) return launch_rows1_k<3, 8, true, 0, 2>(pl, o, s, name);
     }
     return MS_ERR_UNSUPPORTED;
@@ -1637,7 +1639,7 @@ bool msm_bwd_weight_applicable(const ConvP& p) {
 // p = mirrored conv of the transposed conv: Cin_T = p.Cout, Cout_T = p.Cin, Lin_T = p.Lout
 bool msm_convt_fwd_applicable(const ConvP& p) {
     const int S = p.stride;
-    if (!(S == 2 || S == 8) || p.K != 2 * S || 2 * p.pad != S || p.dil != 1 || p.groups != 1) return false;
+    if (!ms_convt_phase_stride(S) || p.K != 2 * S || 2 * p.pad != S || p.dil != 1 || p.groups != 1) return false;
     if (p.Cout % 8 || p.Cin < 32 || (p.Cin * S) % 32) return false;
     if ((long long)p.B * p.Lin >= (1LL << 31)) return false;
     RowP q;
@@ -1713,7 +1715,7 @@ int msm_convt1d_fwd(const ConvP& p, const float* x, const float* w, const float*
 // ---- ConvTranspose1d backward (p = mirrored conv: Cin_T = p.Cout, Cout_T = p.Cin, Lin_T = p.Lout)
 bool msm_convt_bwd_applicable(const ConvP& p) {
     const int S = p.stride;
-    if (!(S == 2 || S == 8) || p.K != 2 * S || 2 * p.pad != S || p.dil != 1 || p.groups != 1) return false;
+    if (!ms_convt_phase_stride(S) || p.K != 2 * S || 2 * p.pad != S || p.dil != 1 || p.groups != 1) return false;
     if (p.Cout < 32 || p.Cin % 8 || (p.Cin * S) % 8) return false;
     if ((long long)p.B * p.Cin * p.Lin >= (1LL << 31) || (long long)p.B * p.Cout * p.Lout >= (1LL << 31)) return false;
     RowP q;

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void k_conv_rows2(Row2P p, const float* __rest
         }
     } else {
         // transposed conv: GEMM row m' = co*S + r is output phase r of channel co; a lane's 4
-        // consecutive accumulator rows are 4 consecutive output samples (S = 8) or 2 x 2 (S = 2)
+        // consecutive accumulator rows are 4 consecutive output samples (S = 8, S = 4) or 2 x 2 (S = 2)
         constexpr int ES = EPI_S > 0 ? EPI_S : 1;
         const int Cout = p.M / ES;
         const size_t Lo = (size_t)p.L * ES;
@@ -380,7 +380,20 @@ __global__ __launch_bounds__(256) void k_conv_rows2(Row2P p, const float* __rest
                     if (!nvalid[j]) continue;
 #pragma unroll
                     for (int rg = 0; rg < 4; ++rg) {
-                        if (EPI_S >= 4) {       // row-in-half 8rg+4h+u = (channel 2rg+h, phase u) for S = 8
+                        if (EPI_S == 4) {       // row-in-half 8rg+4h+u = (channel 4rg+2h+u/2, phase u%2): the two sub-tiles
+                                                // hold the low and the high phase pair of one input position -- 16 bytes
+#pragma unroll
+                            for (int c = 0; c < 2; ++c) {
+                                const int co = mg / 4 + 4 * rg + 2 * h + c;
+                                const float bv = bias ? bias[co] : 0.f;
+                                float4 v;
+                                v.x = ms_apply_act(acc[0][j][4 * rg + 2 * c + 0] + bv, p.act, p.slope);
+                                v.y = ms_apply_act(acc[0][j][4 * rg + 2 * c + 1] + bv, p.act, p.slope);
+                                v.z = ms_apply_act(acc[TM - 1][j][4 * rg + 2 * c + 0] + bv, p.act, p.slope);
+                                v.w = ms_apply_act(acc[TM - 1][j][4 * rg + 2 * c + 1] + bv, p.act, p.slope);
+                                *reinterpret_cast<float4*>(Y + ((size_t)ob[j] * Cout + co) * Lo + (size_t)ot[j] * 4) = v;
+                            }
+                        } else if (EPI_S >= 4) {       // row-in-half 8rg+4h+u = (channel 2rg+h, phase u) for S = 8
                             const int co = mg / ES + (8 * rg + 4 * h) / (ES / 2);
                             const float bv = bias ? bias[co] : 0.f;
                             float* yp = Y + ((size_t)ob[j] * Cout + co) * Lo + (size_t)ot[j] * ES;
@@ -503,17 +516,17 @@ bool msr2_supported(int tile, int K, int CC, int act_mode, int epi_s, const Row2
     }
     if (p.L % 4) return false;
     if (in_s != 1) {      // transposed-conv backward data: phase-split input rows, pre-packed weights
-        if (!(in_s == 2 || in_s == 8) || (act_mode != 2 && act_mode != 0) || K != 2 || CC != 8 || epi_s != 0) return false;
+        if (!(in_s == 2 || in_s == 4 || in_s == 8) || (act_mode != 2 && act_mode != 0) || K != 2 || CC != 8 || epi_s != 0) return false;
         const int bnI = tile == MSR2_32x256 ? 256 : (tile == MSR2_64x64 ? 64 : 128);
         return p.R * (CC / in_s) * ((p.SS * in_s + 6) / 4) <= 256 * msr2_nxq(CC, bnI);
     }
     if (act_mode == 2 || (act_mode == 3 && K != 2)) return false;
     // transposed-conv forward with the two live taps per phase (act_mode 3: LeakyReLU in front, on load):
     // 128x128 tile or 64x128 as 1x4 waves, whole 64-row groups
-    if (K == 2) return CC == 8 && (act_mode == 0 || act_mode == 3) && (epi_s == 2 || epi_s == 8) &&
+    if (K == 2) return CC == 8 && (act_mode == 0 || act_mode == 3) && (epi_s == 2 || epi_s == 4 || epi_s == 8) &&
                        (tile == MSR2_128x128 || tile == MSR2_64x128) && p.M % 64 == 0 &&
                        CC * (p.R * ((p.SS + 6) / 4)) <= 256 * msr2_nxq(CC, 128);
-    const bool k3 = K == 3 && (CC == 8 || CC == 16) && (epi_s == 0 || ((epi_s == 2 || epi_s == 8) && CC == 8 && act_mode == 0));
+    const bool k3 = K == 3 && (CC == 8 || CC == 16) && (epi_s == 0 || ((epi_s == 2 || epi_s == 4 || epi_s == 8) && CC == 8 && act_mode == 0));
     // (k5 forward: the first-generation kernel measured 8 % faster, 194 vs 212 us at B*L = 2048)
     const bool k5 = K == 5 && CC == 16 && epi_s == 0 && act_mode == 1;
     // pointwise convs (shortcuts): measured 44 vs 60 us on the 128-channel layer, but no better than the
@@ -530,16 +543,20 @@ int msr2_launch(int tile, int K, int CC, int act_mode, int epi_s, const Row2P& p
                 float* Yact, dim3 grid, hipStream_t s, int in_s, char* name) {
     if (in_s == 0) return launch_tile<5, 16, 1, 0, 0>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
     if (in_s == 8 && act_mode == 2) return launch_tile<2, 8, 2, 0, 8>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (in_s == 4 && act_mode == 2) return launch_tile<2, 8, 2, 0, 4>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
     if (in_s == 2 && act_mode == 2) return launch_tile<2, 8, 2, 0, 2>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
     if (in_s == 8) return launch_tile<2, 8, 0, 0, 8>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
+    if (in_s == 4) return launch_tile<2, 8, 0, 0, 4>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
     if (in_s == 2) return launch_tile<2, 8, 0, 0, 2>(tile, p, X, Xact, W, bias, res, Y, Yact, grid, s, name);
 #define MSR2_HALF(A)                                                                                              \
     if (K == 2 && CC == 8 && act_mode == A && tile == MSR2_128x128) {                                            \
         if (epi_s == 8) return launch_inst<2, 2, 2, 2, 2, 8, A, 8>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
+        if (epi_s == 4) return launch_inst<2, 2, 2, 2, 2, 8, A, 4>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
         if (epi_s == 2) return launch_inst<2, 2, 2, 2, 2, 8, A, 2>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
     }                                                                                                            \
     if (K == 2 && CC == 8 && act_mode == A && tile == MSR2_64x128) {   /* 64 x 128 as 1 x 4 waves of 64 x 32 */  \
         if (epi_s == 8) return launch_inst<1, 4, 2, 1, 2, 8, A, 8>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
+        if (epi_s == 4) return launch_inst<1, 4, 2, 1, 2, 8, A, 4>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
         if (epi_s == 2) return launch_inst<1, 4, 2, 1, 2, 8, A, 2>(p, X, Xact, W, bias, res, Y, Yact, grid, s, name);  \
     }
     MSR2_HALF(0)
@@ -552,6 +569,7 @@ int msr2_launch(int tile, int K, int CC, int act_mode, int epi_s, const Row2P& p
     }
     if (K == 3 && CC == 8 && act_mode == 0) {
         if (epi_s == 2) MSR2_GO(3, 8, 0, 2);
+        if (epi_s == 4) MSR2_GO(3, 8, 0, 4);
         if (epi_s == 8) MSR2_GO(3, 8, 0, 8);
     }
     if (K == 1 && CC == 32 && epi_s == 0 && act_mode == 0) MSR2_GO(1, 32, 0, 0);

@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256) void k_conv_rows3(Row2P p, const float* __rest
 // Group layout: WGM x (4 / WGM) waves of TM x TN sub-tiles: 2 x 2 waves of TM x 2 (64 or 128 rows) or, for the
 // 32-channel layers, 1 x 4 waves of 1 x 1 (32 rows); 128 columns per group either way.
 //
-// HS = S > 0: ConvTranspose1d forward (stride S = 2 / 8, kernel 2S, padding S/2) as a conv over the input rows with
+// HS = S > 0: ConvTranspose1d forward (stride S = 2 / 4 / 8, kernel 2S, padding S/2) as a conv over the input rows with
 // M = Cout * S GEMM rows packed by k_pack_convt_w2 in blocks of 64 = [32 low-phase | 32 high-phase] rows: every
 // phase has TWO live taps of the 3-column window -- columns {0, 1} for the low phases, {1, 2} for the high ones --
 // so a 32-row sub-tile multiplies two weight taps (A has K = 2) against the window columns offset by its half.
@@ -689,6 +689,9 @@ __global__ __launch_bounds__(512) void k_conv_rows3p(Row2P p, const float* __res
             if (S == 8) {
                 const float* tr = Ts + (b64 * 64 + (ph0 / SH) * 32 + cl * SH) * TP + nl;
                 v = make_float4(tr[0], tr[TP], tr[2 * TP], tr[3 * TP]);
+            } else if (S == 4) {     // one vector per input position: its low phase pair, then the high one
+                const float* tr = Ts + (b64 * 64 + cl * SH) * TP + nl;
+                v = make_float4(tr[0], tr[TP], tr[32 * TP], tr[33 * TP]);
             } else {
                 const float* tr = Ts + (b64 * 64 + cl) * TP + nl;
                 v = make_float4(tr[0], tr[32 * TP], tr[1], tr[32 * TP + 1]);
@@ -877,7 +880,7 @@ int msr3p_launch(int bm, int K, int act_mode, const Row2P& p, const float* X, co
 bool msr3p_convt_supported(int bm, int S, const Row2P& p) {
     if (!ms_switch_on("MSYNTH_ROWS3P")) return false;
     if (!ms_switch_on("MSYNTH_CONVT3")) return false;    // tuning / test switch (0: fp32-MFMA transposed-conv kernel)
-    if ((S != 2 && S != 8) || (bm != 64 && bm != 128)) return false;
+    if ((S != 2 && S != 4 && S != 8) || (bm != 64 && bm != 128)) return false;
     if (p.M % 64 || p.CK % CC3 || p.CKs % CC3 || p.dil != 1 || p.off0 != -1) return false;
     if (!rows_vec(p) || (long long)p.B * (p.M / S) * p.L * S >= (1ll << 31)) return false;
     const int nvt = p.R * ((p.SS + 6) / 4);
@@ -892,10 +895,12 @@ int msr3p_convt_launch(int bm, int S, bool in_act, const Row2P& p, const float* 
     return launch_pair<WGM_, TM_, 2, 3, 0, S_, IA_>(p, X, nullptr, W, bias, nullptr, Y, nullptr, grid, s, name)
     if (bm == 128) {
         if (S == 8) { if (in_act) MS3T(2, 2, 8, true); MS3T(2, 2, 8, false); }
+        if (S == 4) { if (in_act) MS3T(2, 2, 4, true); MS3T(2, 2, 4, false); }
         if (in_act) MS3T(2, 2, 2, true);
         MS3T(2, 2, 2, false);
     }
     if (S == 8) { if (in_act) MS3T(2, 1, 8, true); MS3T(2, 1, 8, false); }
+    if (S == 4) { if (in_act) MS3T(2, 1, 4, true); MS3T(2, 1, 4, false); }
     if (in_act) MS3T(2, 1, 2, true);
     MS3T(2, 1, 2, false);
 #undef MS3T

@@ -16,6 +16,10 @@ static inline int ms_switch_int(const char* name, int dflt) {    // the variable
     return e ? atoi(e) : dflt;
 }
 static inline bool ms_switch_on(const char* name) { return ms_switch_int(name, 1) != 0; }   // on unless set to 0
+// Strides the phase-split transposed-conv kernels (K = 2S, padding S/2) exist for, in all three passes
+static inline bool ms_convt_phase_stride(int S) {
+    return S == 2 || S == 8 || (S == 4 && ms_switch_on("MSYNTH_CONVT_S4"));   // tuning / test switch (0: S = 4 on the direct kernels)
+}
 
 #define MS_CHECK_LAUNCH()                                   \
     do {                                                    \

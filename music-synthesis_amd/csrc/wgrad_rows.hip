@@ -997,7 +997,7 @@ WrPlan plan_wrows_t(const ConvP& c) {
     WrPlan q;
     q.ok = false;
     const int S = c.stride, CinT = c.Cout, CoutT = c.Cin, LinT = c.Lout;
-    if (!(S == 2 || S == 8) || c.K != 2 * S || 2 * c.pad != S || c.dil != 1 || c.groups != 1) return q;
+    if (!ms_convt_phase_stride(S) || c.K != 2 * S || 2 * c.pad != S || c.dil != 1 || c.groups != 1) return q;
     if (CinT < 64 || (CoutT * S) % CB || LinT % 4) return q;
     if ((long long)c.B * CinT * LinT >= (1LL << 31) || (long long)c.B * CoutT * S * LinT >= (1LL << 31)) return q;
     WrP& p = q.p;
@@ -1075,9 +1075,16 @@ int msw_convt_dwq(const ConvP& c, const float* x, const float* gy, const float* 
     if (c.in_act && y_act) return MS_ERR_UNSUPPORTED;
     float* partial = (float*)ws;
     const int S = c.stride;
-    if (c.in_act) { if (S == 8) launch_wrows_t2<5, 8>(q, gy, y_act, x, partial, s); else launch_wrows_t2<5, 2>(q, gy, y_act, x, partial, s); }
-    else if (y_act) { if (S == 8) launch_wrows_t2<3, 8>(q, gy, y_act, x, partial, s); else launch_wrows_t2<3, 2>(q, gy, y_act, x, partial, s); }
-    else { if (S == 8) launch_wrows_t2<0, 8>(q, gy, y_act, x, partial, s); else launch_wrows_t2<0, 2>(q, gy, y_act, x, partial, s); }
+#define MS_WT2(AK)                                                               \
+    do {                                                                         \
+        if (S == 8) launch_wrows_t2<AK, 8>(q, gy, y_act, x, partial, s);         \
+        else if (S == 4) launch_wrows_t2<AK, 4>(q, gy, y_act, x, partial, s);    \
+        else launch_wrows_t2<AK, 2>(q, gy, y_act, x, partial, s);                \
+    } while (0)
+    if (c.in_act) MS_WT2(5);
+    else if (y_act) MS_WT2(3);
+    else MS_WT2(0);
+#undef MS_WT2
     MS_CHECK_LAUNCH();
     return msm_wgrad_reduce(partial, q.stride_floats, q.nsplit, (size_t)q.p.M * q.p.CK * 3, q.p.M, dwq,
                             (float*)nullptr, 0.f, s);

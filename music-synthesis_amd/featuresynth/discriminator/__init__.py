@@ -1,2 +1,3 @@
 from .full import FullDiscriminator
 from .melgan import MelGanDiscriminator
+from .multiscale import ChannelDiscriminator, MultiScaleDiscriminator, MultiScaleMultiResDiscriminator

@@ -3,3 +3,6 @@ from .experiment import Experiment
 from .melgan import MultiScaleMelGanExperiment
 from .realmelgan import RealMelGanExperiment
 from .featureexperiment import TwoDimGeneratorFeatureExperiment
+from .multiscale import (MultiScaleMultiResGroupedFeaturesExperiment, MultiScaleNoDeRecompose,
+                         MultiScaleNoDeRecomposeShortKernels, MultiScaleNoDeRecomposeUnconditionedShortKernel,
+                         MultiScaleWithDeRecompose)

@@ -1,1 +1,2 @@
 from .full import MelGanGenerator
+from .multiscale import ChannelGenerator, MultiScaleGenerator

@@ -215,6 +215,31 @@ class DilatedStack(nn.Module):
         return (features, x) if return_features else x
 
 
+class LearnedUpSample(nn.Module):
+    """Reference util/modules.py:168-188: a bias-free ConvTranspose1d(kernel_size, stride = scale_factor, padding =
+    (kernel_size - scale_factor) // 2) under the attribute `conv`, followed by `activation`.  Only LeakyReLU(0.2) (the
+    one the multi-scale generator uses) is fused; the `activation` callable is kept for the signature and checked
+    against it on first use."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, scale_factor, activation):
+        super().__init__()
+        self.activation = activation
+        self.conv = HipConvTranspose1d(in_channels, out_channels, kernel_size, stride=scale_factor,
+                                       padding=(kernel_size - scale_factor) // 2, bias=False, activation="lrelu")
+        self._act_checked = False
+
+    def _check_activation(self, device):
+        if not self._act_checked:
+            probe = torch.tensor([-2.0, 0.0, 3.0], device=device)
+            if not torch.allclose(self.activation(probe), torch.nn.functional.leaky_relu(probe, 0.2)):
+                raise NotImplementedError("LearnedUpSample (MI355X build): only LeakyReLU(0.2) is fused")
+            self._act_checked = True
+
+    def forward(self, x):
+        self._check_activation(x.device)
+        return self.conv(x)
+
+
 class Fused(nn.Module):
     """Parameter-free placeholder that keeps the reference's nn.Sequential indices (and therefore
     its state_dict keys) for a pad / activation layer that is fused into the neighbouring conv."""
